@@ -19,7 +19,10 @@ With --gpus N > 1 and no launcher environment (RANK / WORLD_SIZE unset) the scri
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free port>`: one rank per GPU,
 the same line on rank 0.  A line never says n_gpus: 1 for --gpus N: a WORLD_SIZE that disagrees with --gpus is an error.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for the fields).
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for the fields).  A plain run sets up, warms up, times the K steps
+and prints the line (`value`, `ms_per_step`, the roofline of the timed launches).  `--full` adds the side measurements that take runs
+of their own: the power probe, `plain_call`, `dense_copy`, `cpu_baseline` and `end_to_end`.  `--dump-outputs DIR` writes what the
+last timed step computed to DIR/*.npy (dump_outputs()).
 
 `--backend gloo --plumbing-only` (tests/test_shard_gloo.py) runs the N > 1 control flow -- rendezvous, barriers, counter
 gather, whole-job arithmetic, the JSON line -- on CPUs with fixed stand-in counters and NO kernel; its line says so and is not
@@ -57,7 +60,7 @@ WORKLOADS = {
 }
 NOTES = {
     "min": "bound by the in-order instruction issue of two waves per SIMD (eight waves per CU: LDS staging) with the board's power cap as a second ceiling 5-8 % "
-           "above it -- the three-wave kernel (k_minimizer_ring) needs 8 % fewer cycles and is clocked 9 % lower; `power` holds this run's board watts and clock "
+           "above it -- the three-wave kernel (k_minimizer_ring) needs 8 % fewer cycles and is clocked 9 % lower; `power` (--full) holds this run's board watts and clock "
            "(every kernel of the library draws 1.26-1.38 kW of the 1.4 kW cap; DESIGN.md 3.1) -- not by HBM; the VALU pipe is ~0.6 full",
     "nt": "HBM-write bound (DESIGN.md 3.2); a plain 16 B/lane fill kernel reaches 5.2-5.9 TB/s on this part",
     "syn": "integer-VALU bound: k_syncmer_pf -- the rolling s-mer hash + a 2(k-s) window per base, then the ~7 selected k-mers of a read hashed from scratch at the end of every unit (round 6; DESIGN.md 3.3)",
@@ -301,6 +304,55 @@ def same_kernel(profiled: str, planned: str) -> bool:
     return all(any(a == b for b in it) for a in re.findall(r"[\w-]+", planned.partition("<")[2]))
 
 
+DUMP_BUDGET = 48 << 20  # bytes of the sampled reads' files (all files together stay under 64 MB)
+DUMP_BLOCK = 256        # consecutive reads per sampled block
+
+
+def dump_outputs(res, out_dir: str, read_len: int, k: int, seed: int):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float64 .npy files (a u64 goes as two u32
+    halves, exact in float64).  The same arguments give the same inputs, so two builds compare file for file.
+      digest.npy          [n_reads, n_tuples, checksum_hi, checksum_lo, short, illegal, first_window_tie, has_non_acgt] of the
+                          whole result (bsk_result_digest: the order-independent checksum covers every tuple)
+      read_index.npy      the sampled reads: blocks of DUMP_BLOCK consecutive reads at seeded positions, ascending
+      status.npy          their status bytes
+      tuples_per_read.npy their tuple counts
+      hash_hi.npy, hash_lo.npy, pos.npy   every tuple of the sampled reads in Next() order (pos: u32 position | strand << 31;
+                          not for kinds without positions)
+    The number of blocks depends on the arguments alone: the most tuples a read can yield (one per k-mer) must fit DUMP_BUDGET."""
+    import numpy as np
+    inf = res.info()
+    n, has_pos = int(inf["n_reads"]), bool(inf["has_pos"])
+    os.makedirs(out_dir, exist_ok=True)
+    dg = res.digest()
+    ck = dg["checksum"]
+    np.save(os.path.join(out_dir, "digest.npy"),
+            np.array([n, dg["n_tuples"], ck >> 32, ck & 0xFFFFFFFF, dg["short"], dg["illegal"], dg["first_window_tie"], dg["has_non_acgt"]],
+                     np.float64))
+    block = min(DUMP_BLOCK, n)
+    per_read = max(read_len - k + 1, 1) * (24 if has_pos else 16) + 24
+    n_blocks = min(n // block, max(1, DUMP_BUDGET // (per_read * block))) if n else 0
+    starts = np.sort(np.random.default_rng(seed).choice(n // block, n_blocks, replace=False)) * block if n_blocks else []
+    idx, status, counts, hashes, poss = [], [], [], [], []
+    for a in starts:
+        offs, st, h, p = res.fetch(int(a), block)
+        idx.append(np.arange(a, a + block, dtype=np.uint64))
+        status.append(st)
+        counts.append(np.diff(offs))
+        hashes.append(h)
+        if p is not None:
+            poss.append(p)
+    cat = (lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dt))
+    h = cat(hashes, np.uint64)
+    out = {"read_index": cat(idx, np.uint64), "status": cat(status, np.uint8), "tuples_per_read": cat(counts, np.uint64),
+           "hash_hi": h >> np.uint64(32), "hash_lo": h & np.uint64(0xFFFFFFFF)}
+    if has_pos:
+        out["pos"] = cat(poss, np.uint32)
+    total = sum(v.size for v in out.values()) * 8
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes of samples (more tuples per read than k-mers?)"
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v.astype(np.float64))
+
+
 def plumbing_counters(rank: int):
     """Stand-in counters of --plumbing-only: [nanoseconds, bases, tuples, first-window-tie reads, non-ACGT reads]."""
     return [int((1.0 + 0.5 * rank) * 1e9), 15_000_000_000 + rank, 2_211_224_063 + 7 * rank, 88 + rank, 0]
@@ -390,15 +442,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="minimizer", choices=sorted(WORKLOADS))
     ap.add_argument("--reads", type=float, default=0, help="override reads per GPU (dev)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the file/host-memory -> host-tuples side measurement")
-    ap.add_argument("--no-power-probe", action="store_true", help="skip the rocm-smi power / clock samples taken while the launch loops after the measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements after the headline: power probe, plain_call, dense_copy, CPU baseline, end_to_end")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: skip the file/host-memory -> host-tuples side measurement")
+    ap.add_argument("--no-power-probe", action="store_true", help="with --full: skip the rocm-smi power / clock samples taken while the launch loops after the measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) to DIR/<name>.npy, float64: see dump_outputs()")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend of the rendezvous / barriers")
     ap.add_argument("--plumbing-only", action="store_true", help="tests: N>1 control flow with stand-in counters, no GPU, no kernel")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.plumbing_only:
+        raise SystemExit("--dump-outputs needs a kernel run: not with --plumbing-only")
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if not launched and (args.gpus > 1 or os.environ.get("BSK_BENCH_SELF_LAUNCH")):  # (BSK_BENCH_SELF_LAUNCH: tests take the self-launched form on a one-GPU box)
         raise SystemExit(self_launch(args.gpus))
@@ -486,6 +546,8 @@ def main():
         dg = res.digest()
         plan = res.plan()
         mine = [int(dt * 1e9), n_reads * read_len, int(res.info()["n_tuples"]), int(dg["first_window_tie"]), int(dg["has_non_acgt"])]
+        if args.dump_outputs and rank == 0:
+            dump_outputs(res, args.dump_outputs, read_len, k, seed)
 
     # whole-job numbers: MAX time over ranks, SUM of units over ranks -- ONE all_gather of five u64 counters per rank
     if world == 1 and not force_comm:
@@ -563,14 +625,15 @@ def main():
                                       "roofline of the committed PMC pass (SQ_INSTS_VALU x the mean issue cost of the kernel's inner-loop instruction mix, "
                                       "scripts/valu_model.py, over the dispatch's SIMD-cycles) and `binding_ceiling` names the larger of the two fractions",
             }
-        if kernel_ms and not args.no_power_probe and not args.plumbing_only:
+        # --full: the side measurements below take runs of their own; a plain run ends with the headline
+        if args.full and kernel_ms and not args.no_power_probe and not args.plumbing_only:
             try:
                 out["roofline"]["power"] = power_probe(eng, batch, p, res, sum(kernel_ms) / len(kernel_ms), local_rank, n_reads * read_len)
             except Exception as e:
                 out["roofline"]["power"] = {"error": repr(e)}
         if not args.plumbing_only:
             out["first_call"] = dict(first_call, note="one-time costs of a context / a fresh result on this rank (wall ms): outside the timed region, reported so that a caller can see them")
-        if world == 1 and kernel_ms and not args.plumbing_only:
+        if args.full and world == 1 and kernel_ms and not args.plumbing_only:
             # what a caller that releases every result and sketches the next batch pays per call: bsk_sketch's wall time on a FRESH result
             # (plan + result arrays + one sizing launch + the totals read back) -- outside `value`, reported beside it.  The first of the
             # three allocates its arrays (the timed result still holds its own); the next ones take over what the one before released.
@@ -586,7 +649,7 @@ def main():
                                              "(the context keeps a released result's arrays for the next one: bsk_ctx::spare, NOTEBOOK 6.7)"}
             except Exception as e:
                 out["plain_call"] = {"error": repr(e)}
-        if world == 1 and kernel_ms and not args.plumbing_only:
+        if args.full and world == 1 and kernel_ms and not args.plumbing_only:
             # what a device-side consumer of the tuples pays on top of the sketch: bsk_result_compact (offsets scanned, the units'
             # slabs squeezed into dense CSR arrays left in HBM; sets.hip, k_gather_groups) -- outside `value`, reported beside it
             try:
@@ -605,9 +668,9 @@ def main():
                                      "sketch_plus_dense_copy": round(n_reads * read_len / ((sum(kernel_ms) / len(kernel_ms)) + c_ms) / 1e6, 2), "unit": out["unit"]}
             except Exception as e:
                 out["dense_copy"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline and not args.plumbing_only:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.plumbing_only:
             out["cpu_baseline"] = cpu_baseline(kind, k, x, read_len, batch)
-        if world == 1 and not args.no_end_to_end and not args.plumbing_only:
+        if args.full and world == 1 and not args.no_end_to_end and not args.plumbing_only:
             try:
                 out["end_to_end"] = end_to_end(kind, p, batch, read_len, int(os.environ.get("BSK_BENCH_STREAMS", "5")))
             except Exception as e:  # never let the side measurement cost the line

@@ -28,6 +28,6 @@ cd "$REPO"
 cp "profiles/$ROUND/valu_model.json" "$OUT/valu_model.json" 2>/dev/null || cp "$(ls profiles/r*/valu_model.json | tail -1)" "$OUT/valu_model.json" 2>/dev/null  # (the VALU issue-cost model: scripts/valu_model.py on the build container, committed with the round before the collection)
 python scripts/profile_post.py "$OUT" "$WORKLOADS" && mkdir -p profiles/$ROUND && cp "$OUT/traffic.json" profiles/$ROUND/traffic.json
 for w in $WORKLOADS; do
-  python bench.py --workload $w --steps 20 --warmup 3 > "$OUT/BENCH_${w}_n1.json" 2> "$OUT/BENCH_${w}_n1.err" || true
+  python bench.py --workload $w --steps 20 --warmup 3 --full > "$OUT/BENCH_${w}_n1.json" 2> "$OUT/BENCH_${w}_n1.err" || true
 done
 ls -la "$OUT"
