@@ -64,6 +64,11 @@ class Params(C.Structure):
                 ("kind", "k", "w", "s", "m", "scale", "canonical", "circular", "codon_table", "frame")]
 
 
+class SearchParams(C.Structure):
+    """bsk_search_params (include/biosketch.h)"""
+    _fields_ = [("min_shared", C.c_uint32), ("reserved", C.c_uint32), ("min_query_cov", C.c_double), ("min_target_cov", C.c_double)]
+
+
 # every symbol include/biosketch.h declares: (name, restype, argtypes)
 _vp = C.c_void_p
 _pp = C.POINTER(C.c_void_p)
@@ -142,6 +147,16 @@ SYMBOLS = [
     ("bsk_sets_fetch", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64]),
     ("bsk_sets_device", C.c_int, [_vp, _pp, _pp]),
     ("bsk_sets_release", None, [_vp]),
+    ("bsk_sets_from_host", C.c_int, [_vp, _vp, C.c_uint64, _vp, _pp]),
+    ("bsk_index_build", C.c_int, [_vp, _vp, _pp]),
+    ("bsk_index_info", C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p, _u64p]),
+    ("bsk_index_release", None, [_vp]),
+    ("bsk_index_search", C.c_int, [_vp, _vp, _vp, C.POINTER(SearchParams), _pp]),
+    ("bsk_hits_info", C.c_int, [_vp, _u64p, _u64p]),
+    ("bsk_hits_plan", C.c_int, [_vp, C.POINTER(C.c_char_p), _u64p]),
+    ("bsk_hits_fetch", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.c_uint64]),
+    ("bsk_hits_device", C.c_int, [_vp, _pp, _pp, _pp]),
+    ("bsk_hits_release", None, [_vp]),
 ]
 SETS_PER_SEQUENCE, SETS_WHOLE_BATCH = 0, 1
 

@@ -1,0 +1,691 @@
+// search.hip -- containment search of sketch sets against a device-resident inverted index (include/biosketch.h "containment
+// search").  For every query set q and target set t: s = |q & t|, listed when it passes the caller's thresholds; CSR hits by query.
+// This is what a kmcp-style consumer does with the sets bsk_result_sets leaves on the device -- the sets never cross the link, only
+// the hits do.
+//
+// Index (bsk_index_build): every (value, target) posting gets the key mix64(value) -- a bijection, so distinct values stay distinct
+// keys, and the keys are uniform whatever the values are (k-mer codes of k = 11 live in the low 22 bits, host-loaded sets can be
+// clustered: a directory over raw top bits would put them all in bucket 0).  One rocprim::radix_sort_pairs<u64, u32> of
+// (key, target): the sort is stable and the input is target-major, so the targets of a key leave ascending.  Run-length of the keys
+// -> keys[U], post_off[U + 1], post_tgt[P]; a directory dir[2^b + 1] of bucket starts over the top b bits of the key, 2^b <= U <
+// 2^(b+1): one or two keys per bucket.
+//
+// Search (bsk_index_search): A. lookups, a group of 16 lanes per query -- mix, one directory entry, a bucket scan -- store every
+// query value's posting range and the query's sum of posting lengths (coalesced); B. scans of those sums give every query a staging
+// span (its hits are at most min(sum, targets)); C. one wavefront per query copies the target ids of its postings into LDS, sorts
+// them (bitonic), counts the runs, applies the threshold and writes (target, shared) ascending into its span; then a scan of the hit
+// counts and a move.  Queries whose sum exceeds the LDS budget (SR_CAP: a genome against genomes, a value held by thousands of
+// targets) are listed and take the large path: (slot << 32) | target keys, the rocprim::radix_sort_keys<u64> sets.hip already
+// instantiates, run-length, threshold.  Exact, and no new template.
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <vector>
+
+#include "biosketch.h"
+#include "host_types.hpp"
+#include "sets_internal.hpp"
+
+struct bsk_index {
+    bsk_ctx *ctx = nullptr;
+    u64 n_targets = 0, n_postings = 0, n_distinct = 0, max_bucket = 0, device_bytes = 0;
+    int bits = 0;              // directory over the top `bits` bits of the mixed key
+    u64 *keys = nullptr;       // [U] distinct mixed keys, ascending
+    u32 *post_off = nullptr;   // [U + 1] postings of key u: post_tgt[post_off[u] .. post_off[u + 1])
+    u32 *post_tgt = nullptr;   // [P] target ids, ascending inside a key
+    u32 *dir = nullptr;        // [2^bits + 1] first key of every bucket
+    u32 *tsize = nullptr;      // [n_targets] |t|
+};
+
+struct bsk_hits {
+    bsk_ctx *ctx = nullptr;
+    u64 n_queries = 0, n_hits = 0, n_large = 0;
+    u64 *offsets = nullptr;  // [n_queries + 1]
+    u32 *target = nullptr, *shared = nullptr;
+    size_t c_offsets = 0, c_target = 0, c_shared = 0;  // bytes allocated (grow-only when the object is re-used)
+    char plan[192] = "";
+};
+
+#define SR_CAP 2048  // target ids pass C holds per query: 8 KB of LDS per wavefront
+#define SR_WAVES 4   // wavefronts per workgroup of pass C
+
+namespace {
+
+// splitmix64's finalizer: every step (xor-shift, odd multiply) is invertible, so distinct values keep distinct keys
+__device__ __forceinline__ u64 mix64(u64 x) {
+    x ^= x >> 30;
+    x *= 0xbf58476d1ce4e5b9ULL;
+    x ^= x >> 27;
+    x *= 0x94d049bb133111ebULL;
+    x ^= x >> 31;
+    return x;
+}
+__device__ __forceinline__ u64 bucket_of(u64 key, int bits) { return bits ? key >> (64 - bits) : 0; }
+
+struct Thr {
+    u32 min_shared;
+    double qc, tc;
+};
+// the contract's expression, term for term (no sum: nothing the compiler could contract)
+__device__ __forceinline__ bool listed(u32 s, u64 qn, u32 tn, const Thr &p) {
+    return s >= p.min_shared && (double)s >= p.qc * (double)qn && (double)s >= p.tc * (double)tn;
+}
+
+// ---- index build ----
+// posting i -> (mix64(value), its target); the target by a binary search over the sets' offsets (a thread per posting: a group per
+// target left most of the device idle on a thousand genome-size targets)
+__global__ __launch_bounds__(256) void k_ix_pairs(const u64 *offs, const u64 *vals, u64 T, u64 P, u64 *key, u32 *tgt) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (u64)gridDim.x * blockDim.x) {
+        u64 lo = 0, hi = T;  // the last set whose first value is <= i: offs[lo] <= i < offs[lo + 1]
+        while (hi - lo > 1) {
+            const u64 mid = (lo + hi) >> 1;
+            if (offs[mid] <= i) lo = mid;
+            else hi = mid;
+        }
+        key[i] = mix64(vals[i]);
+        tgt[i] = (u32)lo;
+    }
+}
+__global__ __launch_bounds__(256) void k_ix_sizes(const u64 *offs, u64 T, u32 *tsize) {
+    for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += (u64)gridDim.x * blockDim.x) tsize[t] = (u32)(offs[t + 1] - offs[t]);
+}
+// flag[i] = 1 iff key i starts a run of equal keys
+__global__ __launch_bounds__(256) void k_run_heads(const u64 *k, u64 n, u32 *flag) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) flag[i] = (i == 0 || k[i] != k[i - 1]) ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_ix_scatter(const u64 *k, const u32 *flag, const u64 *pos, u64 P, u64 *keys, u32 *post_off) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (u64)gridDim.x * blockDim.x) {
+        if (flag[i]) {
+            keys[pos[i]] = k[i];
+            post_off[pos[i]] = (u32)i;
+        }
+        if (i == 0) post_off[pos[P]] = (u32)P;
+    }
+}
+// dir[j] = the first key whose bucket is >= j (j = 0 .. 2^bits): key u writes the entries between its predecessor's bucket and its own
+__global__ __launch_bounds__(256) void k_ix_dir(const u64 *keys, u64 U, int bits, u32 *dir) {
+    for (u64 u = (u64)blockIdx.x * blockDim.x + threadIdx.x; u <= U; u += (u64)gridDim.x * blockDim.x) {
+        const u64 b = u < U ? bucket_of(keys[u], bits) : (1ULL << bits);
+        const u64 j0 = u == 0 ? 0 : bucket_of(keys[u - 1], bits) + 1;
+        for (u64 j = j0; j <= b; ++j) dir[j] = (u32)u;
+    }
+}
+__global__ __launch_bounds__(256) void k_ix_maxb(const u32 *dir, u64 nb, u64 *mx) {
+    u32 m = 0;
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < nb; j += (u64)gridDim.x * blockDim.x) {
+        const u32 d = dir[j + 1] - dir[j];
+        m = d > m ? d : m;
+    }
+    m = wave_max_u32(m);
+    if ((threadIdx.x & 63) == 0 && m) atomicMax((unsigned long long *)mx, (unsigned long long)m);
+}
+
+// ---- search ----
+// A: a group of 16 lanes per query; rng[i] = (first posting << 32) | posting count of query value i (0: not in the index),
+// qsum[q] = the query's sum of posting counts
+__global__ __launch_bounds__(256) void k_sr_lookup(const u64 *qoff, const u64 *qvals, u64 nq, const u64 *keys, const u32 *post_off, const u32 *dir,
+                                                   int bits, u64 *rng, u64 *qsum) {
+    const u64 grp = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 4, ng = ((u64)gridDim.x * blockDim.x) >> 4;
+    const u32 l = threadIdx.x & 15;
+    for (u64 q = grp; q < nq; q += ng) {
+        const u64 a = qoff[q], e = qoff[q + 1];
+        u64 sum = 0;
+        for (u64 i = a + l; i < e; i += 16) {
+            const u64 k = mix64(qvals[i]);
+            const u64 j = bucket_of(k, bits);
+            const u32 lo = dir[j], hi = dir[j + 1];
+            u64 r = 0;
+            for (u32 u = lo; u < hi; ++u) {
+                const u64 ku = keys[u];
+                if (ku >= k) {
+                    if (ku == k) {
+                        const u32 s = post_off[u];
+                        r = ((u64)s << 32) | (post_off[u + 1] - s);
+                    }
+                    break;
+                }
+            }
+            rng[i] = r;
+            sum += (u32)r;
+        }
+        sum += __shfl_xor(sum, 8, 16);
+        sum += __shfl_xor(sum, 4, 16);
+        sum += __shfl_xor(sum, 2, 16);
+        sum += __shfl_xor(sum, 1, 16);
+        if (l == 0) qsum[q] = sum;
+    }
+}
+struct StageOf {  // a query's staging span: it lists at most min(sum of its posting counts, targets) hits
+    const u64 *qsum;
+    u64 T;
+    __device__ __forceinline__ u64 operator()(u64 q) const { return qsum[q] < T ? qsum[q] : T; }
+};
+struct LargeOf {  // queries beyond pass C's LDS: their count (count_only) or their target ids
+    const u64 *qsum;
+    bool count_only;
+    __device__ __forceinline__ u64 operator()(u64 q) const { return qsum[q] > SR_CAP ? (count_only ? 1 : qsum[q]) : 0; }
+};
+__global__ __launch_bounds__(256) void k_sr_list_large(const u64 *qsum, u64 nq, const u64 *lslot, u32 *lq) {
+    for (u64 q = (u64)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (u64)gridDim.x * blockDim.x)
+        if (qsum[q] > SR_CAP) lq[lslot[q]] = (u32)q;
+}
+
+// C: one wavefront per query of at most SR_CAP target ids: collect them in LDS, bitonic sort, runs = shared counts, threshold,
+// (target, shared) ascending into the query's staging span; hcnt[q] = hits (0 for the large queries: the large path overwrites it)
+__global__ __launch_bounds__(64 * SR_WAVES) void k_sr_small(const u64 *qoff, const u64 *rng, const u64 *qsum, u64 nq, const u32 *post_tgt,
+                                                            const u32 *tsize, const u64 *stage_off, Thr thr, u32 *st_tgt, u32 *st_sh, u64 *hcnt) {
+    __shared__ u32 lds[SR_WAVES][SR_CAP];
+    u32 *buf = lds[threadIdx.x >> 6];
+    const int lane = threadIdx.x & 63;
+    const u64 lt_mask = (1ULL << lane) - 1;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((u64)gridDim.x * blockDim.x) >> 6;
+    for (u64 q = wave; q < nq; q += nw) {
+        const u64 n64 = qsum[q];
+        if (n64 == 0 || n64 > SR_CAP) {
+            if (lane == 0) hcnt[q] = 0;
+            continue;
+        }
+        const u32 n = (u32)n64;
+        const u64 a = qoff[q], e = qoff[q + 1];
+        u32 base = 0;
+        for (u64 i0 = a; i0 < e; i0 += 64) {
+            const u64 i = i0 + lane;
+            const u64 r = i < e ? rng[i] : 0;
+            const u32 len = (u32)r, s = (u32)(r >> 32);
+            const u32 incl = wave_incl_scan_u32(len, lane);
+            const u32 d = base + incl - len;  // d + len <= n <= SR_CAP: the sums are the lookups' own
+            for (u32 t = 0; t < len; ++t) buf[d + t] = post_tgt[s + t];
+            base += (u32)__builtin_amdgcn_readlane((int)incl, 63);
+        }
+        const u32 n2 = n <= 1 ? 1u : 1u << (32 - __builtin_clz(n - 1));  // <= SR_CAP (a power of two)
+        for (u32 i = n + lane; i < n2; i += 64) buf[i] = 0xffffffffu;  // (target ids are < 2^32 - 1)
+        wave_sync_lds();
+        for (u32 k = 2; k <= n2; k <<= 1) {
+            for (u32 j = k >> 1; j > 0; j >>= 1) {
+                for (u32 i = lane; i < n2; i += 64) {
+                    const u32 p = i ^ j;
+                    if (p > i) {
+                        const u32 x = buf[i], y = buf[p];
+                        if ((x > y) == ((i & k) == 0)) {
+                            buf[i] = y;
+                            buf[p] = x;
+                        }
+                    }
+                }
+                wave_sync_lds();
+            }
+        }
+        const u64 out = stage_off[q], qn = e - a;
+        u32 nh = 0;
+        for (u32 i0 = 0; i0 < n; i0 += 64) {
+            const u32 i = i0 + lane;
+            bool keep = false;
+            u32 x = 0, c = 0;
+            if (i < n) {
+                x = buf[i];
+                if (i == 0 || buf[i - 1] != x) {
+                    c = 1;
+                    while (i + c < n && buf[i + c] == x) ++c;
+                    keep = listed(c, qn, tsize[x], thr);
+                }
+            }
+            const u64 m = __ballot(keep);
+            if (keep) {
+                const u64 o = out + nh + (u32)__builtin_popcountll(m & lt_mask);
+                st_tgt[o] = x;
+                st_sh[o] = c;
+            }
+            nh += (u32)__builtin_popcountll(m);
+        }
+        if (lane == 0) hcnt[q] = nh;
+        wave_sync_lds();  // every lane is done with the buffer before the next query fills it
+    }
+}
+
+// large path: one wavefront per listed query writes (slot << 32) | target for every posting of its values at loff[q]; values with
+// long posting lists (a value held by thousands of targets) are copied by the whole wavefront
+__global__ __launch_bounds__(256) void k_lg_emit(const u64 *qoff, const u64 *rng, const u32 *lq, u64 nl, const u64 *loff, const u32 *post_tgt, u64 *lkeys) {
+    const int lane = threadIdx.x & 63;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((u64)gridDim.x * blockDim.x) >> 6;
+    for (u64 slot = wave; slot < nl; slot += nw) {
+        const u32 q = lq[slot];
+        const u64 a = qoff[q], e = qoff[q + 1], hi = slot << 32;
+        u64 dst = loff[q];
+        for (u64 i0 = a; i0 < e; i0 += 64) {
+            const u64 i = i0 + lane;
+            const u64 r = i < e ? rng[i] : 0;
+            const u32 len = (u32)r, s = (u32)(r >> 32);
+            const u32 incl = wave_incl_scan_u32(len, lane);  // (the ranges of distinct values are disjoint: sums stay below 2^32)
+            const u32 ex = incl - len;
+            if (len <= 64)
+                for (u32 t = 0; t < len; ++t) lkeys[dst + ex + t] = hi | post_tgt[s + t];
+            u64 big = __ballot(len > 64);
+            while (big) {
+                const int src = __builtin_ctzll(big);
+                big &= big - 1;
+                const u32 s2 = (u32)__builtin_amdgcn_readlane((int)s, src), len2 = (u32)__builtin_amdgcn_readlane((int)len, src),
+                          ex2 = (u32)__builtin_amdgcn_readlane((int)ex, src);
+                for (u32 t = lane; t < len2; t += 64) lkeys[dst + ex2 + t] = hi | post_tgt[s2 + t];
+            }
+            dst += (u32)__builtin_amdgcn_readlane((int)incl, 63);
+        }
+    }
+}
+// rstart[ridx[i]] = i at every run head of the sorted keys, rstart[R] = L
+__global__ __launch_bounds__(256) void k_lg_runs(const u32 *flag, const u64 *ridx, u64 L, u64 *rstart) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < L; i += (u64)gridDim.x * blockDim.x) {
+        if (flag[i]) rstart[ridx[i]] = i;
+        if (i == 0) rstart[ridx[L]] = L;
+    }
+}
+// run r = (slot, target) shared by rstart[r + 1] - rstart[r] values: keep[r] (0 for r >= R), sfirst[slot] = its first run
+__global__ __launch_bounds__(256) void k_lg_keep(const u64 *k, const u64 *rstart, const u64 *ridx, u64 L, const u32 *lq, const u64 *qoff, const u32 *tsize,
+                                                 Thr thr, u32 *keep, u64 *sfirst) {
+    const u64 R = ridx[L];
+    for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < L; r += (u64)gridDim.x * blockDim.x) {
+        if (r >= R) {
+            keep[r] = 0;
+            continue;
+        }
+        const u64 s0 = rstart[r], key = k[s0], slot = key >> 32;
+        const u32 q = lq[slot];
+        keep[r] = listed((u32)(rstart[r + 1] - s0), qoff[q + 1] - qoff[q], tsize[(u32)key], thr) ? 1u : 0u;
+        if (r == 0 || (k[rstart[r - 1]] >> 32) != slot) sfirst[slot] = r;
+    }
+}
+__global__ __launch_bounds__(256) void k_lg_place(const u64 *k, const u64 *rstart, const u64 *ridx, u64 L, const u32 *keep, const u64 *kpos, const u64 *sfirst,
+                                                  const u32 *lq, const u64 *stage_off, u32 *st_tgt, u32 *st_sh, u64 *hcnt) {
+    const u64 R = ridx[L];
+    for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < R; r += (u64)gridDim.x * blockDim.x) {
+        const u64 s0 = rstart[r], key = k[s0], slot = key >> 32;
+        const u32 q = lq[slot];
+        const u64 f = kpos[sfirst[slot]];
+        if (keep[r]) {
+            const u64 o = stage_off[q] + (kpos[r] - f);
+            st_tgt[o] = (u32)key;
+            st_sh[o] = (u32)(rstart[r + 1] - s0);
+        }
+        if (r + 1 == R || (k[rstart[r + 1]] >> 32) != slot) hcnt[q] = kpos[r + 1] - f;
+    }
+}
+
+// final placement: query q's hits [stage_off[q], +hcnt[q]) -> [off[q], ...); a group of 16 lanes per query
+__global__ __launch_bounds__(256) void k_sr_move(const u64 *stage_off, const u64 *off, const u64 *hcnt, u64 nq, const u32 *st_tgt, const u32 *st_sh,
+                                                 u32 *tgt, u32 *sh) {
+    const u64 grp = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 4, ng = ((u64)gridDim.x * blockDim.x) >> 4;
+    for (u64 q = grp; q < nq; q += ng) {
+        const u64 s0 = stage_off[q], d0 = off[q], c = hcnt[q];
+        for (u64 i = threadIdx.x & 15; i < c; i += 16) {
+            tgt[d0 + i] = st_tgt[s0 + i];
+            sh[d0 + i] = st_sh[s0 + i];
+        }
+    }
+}
+
+unsigned grid_for(const bsk_ctx *ctx, u64 items, u64 per_block, u64 blocks_per_cu) {
+    const u64 g = (items + per_block - 1) / per_block;
+    return (unsigned)std::max<u64>(1, std::min<u64>(g, (u64)ctx->cus * blocks_per_cu));
+}
+
+// device temporaries of one call, freed on every way out
+struct Temps {
+    std::vector<void *> p;
+    ~Temps() {
+        for (void *x : p) (void)hipFree(x);
+    }
+    hipError_t get(void **out, size_t bytes) {
+        *out = nullptr;
+        const hipError_t e = hipMalloc(out, bytes ? bytes : 8);
+        if (e == hipSuccess) p.push_back(*out);
+        return e;
+    }
+};
+// a grow-only temporary of the context (slots 10, 11, 15, 30, 31: the search's), carved into aligned pieces
+hipError_t pool_get(bsk_ctx *ctx, int slot, size_t bytes, void **out) {
+    if (ctx->tmp_cap[slot] < bytes || !ctx->tmp[slot]) {
+        (void)hipFree(ctx->tmp[slot]);
+        ctx->tmp[slot] = nullptr;
+        ctx->tmp_cap[slot] = 0;
+        const size_t want = bytes + bytes / 4 + 256;
+        const hipError_t e = hipMalloc(&ctx->tmp[slot], want);
+        if (e != hipSuccess) return e;
+        ctx->tmp_cap[slot] = want;
+    }
+    *out = ctx->tmp[slot];
+    return hipSuccess;
+}
+struct Carve {
+    size_t bytes = 0;
+    template <class T>
+    size_t add(u64 n) {  // offset of an array of n T, 256-byte aligned
+        const size_t at = bytes;
+        bytes += ((n ? n : 1) * sizeof(T) + 255) & ~(size_t)255;
+        return at;
+    }
+};
+template <class T>
+T *at(void *base, size_t off) {
+    return reinterpret_cast<T *>(static_cast<char *>(base) + off);
+}
+
+}  // namespace
+
+extern "C" int bsk_sets_from_host(bsk_ctx *ctx, const uint64_t *offsets, uint64_t n_sets, const uint64_t *values, bsk_sets **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !offsets || !out) return fail_arg(ctx, "bsk_sets_from_host: null argument");
+    if (offsets[0] != 0) return fail_arg(ctx, "bsk_sets_from_host: offsets[0] != 0");
+    if (offsets[n_sets] && !values) return fail_arg(ctx, "bsk_sets_from_host: null values");
+    for (u64 s = 0; s < n_sets; ++s)  // (first: then every offset is <= offsets[n_sets], the number of values)
+        if (offsets[s + 1] < offsets[s]) return fail_arg(ctx, "bsk_sets_from_host: offsets decrease");
+    for (u64 s = 0; s < n_sets; ++s)
+        for (u64 i = offsets[s] + 1; i < offsets[s + 1]; ++i)
+            if (values[i] <= values[i - 1]) return fail_arg(ctx, "bsk_sets_from_host: values not strictly ascending inside a set");
+    const u64 N = offsets[n_sets];
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    bsk_sets *s = new (std::nothrow) bsk_sets();
+    if (!s) return BSK_ERR_NOMEM;
+    s->ctx = ctx;
+    s->n_sets = n_sets;
+    s->n_values = N;
+    hipError_t e = hipMalloc(&s->offsets, (n_sets + 1) * 8);
+    if (e == hipSuccess) {
+        s->c_offsets = (n_sets + 1) * 8;
+        e = hipMalloc(&s->values, (N ? N : 1) * 8);
+    }
+    if (e == hipSuccess) {
+        s->c_values = (N ? N : 1) * 8;
+        e = hipMemcpyAsync(s->offsets, offsets, (n_sets + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+    }
+    if (e == hipSuccess && N) e = hipMemcpyAsync(s->values, values, N * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (the caller's buffers are not retained)
+    if (e != hipSuccess) {
+        bsk_sets_release(s);
+        return fail_hip(ctx, e, "bsk_sets_from_host");
+    }
+    *out = s;
+    return BSK_OK;
+}
+
+extern "C" void bsk_index_release(bsk_index *ix) {
+    if (!ix) return;
+    if (ix->ctx) (void)hipSetDevice(ix->ctx->device);
+    (void)hipFree(ix->keys);
+    (void)hipFree(ix->post_off);
+    (void)hipFree(ix->post_tgt);
+    (void)hipFree(ix->dir);
+    (void)hipFree(ix->tsize);
+    delete ix;
+}
+
+extern "C" int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !targets || !out) return fail_arg(ctx, "bsk_index_build: null argument");
+    if (targets->ctx != ctx) return fail_arg(ctx, "bsk_index_build: the sets belong to another context");
+    const u64 T = targets->n_sets, P = targets->n_values;
+    if (T >= (1ULL << 32) || P >= (1ULL << 32)) {
+        ctx->err = "bsk_index_build: 2^32 targets or postings or more";
+        return BSK_ERR_UNSUPPORTED;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    bsk_index *ix = new (std::nothrow) bsk_index();
+    if (!ix) return BSK_ERR_NOMEM;
+    std::unique_ptr<bsk_index, void (*)(bsk_index *)> hold(ix, bsk_index_release);
+    ix->ctx = ctx;
+    ix->n_targets = T;
+    ix->n_postings = P;
+    Temps tmp;
+    u64 *kin = nullptr, *kout = nullptr, *pos = nullptr, *part = nullptr, *tot = nullptr;
+    u32 *tin = nullptr, *flag = nullptr;
+    HIPCHK(ctx, hipMalloc(&ix->post_tgt, (P ? P : 1) * 4));
+    HIPCHK(ctx, hipMalloc(&ix->tsize, (T ? T : 1) * 4));
+    HIPCHK(ctx, tmp.get((void **)&tot, 64));
+    HIPCHK(ctx, hipMemsetAsync(tot, 0, 64, st));
+    if (T) {
+        hipLaunchKernelGGL(k_ix_sizes, dim3(grid_for(ctx, T, 256, 8)), dim3(256), 0, st, targets->offsets, T, ix->tsize);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    u64 U = 0;
+    if (P) {
+        HIPCHK(ctx, tmp.get((void **)&kin, (P + 1) * 8));
+        HIPCHK(ctx, tmp.get((void **)&kout, P * 8));
+        HIPCHK(ctx, tmp.get((void **)&tin, P * 4));
+        hipLaunchKernelGGL(k_ix_pairs, dim3(grid_for(ctx, P, 256, 16)), dim3(256), 0, st, targets->offsets, targets->values, T, P, kin, tin);
+        HIPCHK(ctx, hipGetLastError());
+        size_t tb = 0;
+        HIPCHK(ctx, rocprim::radix_sort_pairs(nullptr, tb, kin, kout, tin, ix->post_tgt, (size_t)P, 0, 64, st));
+        void *stmp = nullptr;
+        HIPCHK(ctx, tmp.get(&stmp, tb));
+        HIPCHK(ctx, rocprim::radix_sort_pairs(stmp, tb, kin, kout, tin, ix->post_tgt, (size_t)P, 0, 64, st));
+        flag = tin;  // (both free after the sort)
+        pos = kin;
+        HIPCHK(ctx, tmp.get((void **)&part, ((P + SCAN_CHUNK - 1) / SCAN_CHUNK + 2) * 8));
+        hipLaunchKernelGGL(k_run_heads, dim3(grid_for(ctx, P, 256, 16)), dim3(256), 0, st, kout, P, flag);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, scan_counts(st, KeepOf{flag}, P, part, pos, tot, (u64 *)nullptr));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        U = ctx->h_pinned[0];
+    }
+    int bits = 0;
+    while (bits < 62 && (2ULL << bits) <= U) ++bits;  // 2^bits <= U < 2^(bits + 1): one or two keys per bucket
+    const u64 nb = 1ULL << bits;
+    ix->bits = bits;
+    ix->n_distinct = U;
+    HIPCHK(ctx, hipMalloc(&ix->keys, (U ? U : 1) * 8));
+    HIPCHK(ctx, hipMalloc(&ix->post_off, (U + 1) * 4));
+    HIPCHK(ctx, hipMalloc(&ix->dir, (nb + 1) * 4));
+    if (P) {
+        hipLaunchKernelGGL(k_ix_scatter, dim3(grid_for(ctx, P, 256, 16)), dim3(256), 0, st, kout, flag, pos, P, ix->keys, ix->post_off);
+        HIPCHK(ctx, hipGetLastError());
+    } else {
+        HIPCHK(ctx, hipMemsetAsync(ix->post_off, 0, 4, st));
+    }
+    hipLaunchKernelGGL(k_ix_dir, dim3(grid_for(ctx, U + 1, 256, 16)), dim3(256), 0, st, ix->keys, U, bits, ix->dir);
+    hipLaunchKernelGGL(k_ix_maxb, dim3(grid_for(ctx, nb, 256, 8)), dim3(256), 0, st, ix->dir, nb, tot + 1);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned + 1, tot + 1, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    ix->max_bucket = ctx->h_pinned[1];
+    ix->device_bytes = (U ? U : 1) * 8 + (U + 1) * 4 + (P ? P : 1) * 4 + (nb + 1) * 4 + (T ? T : 1) * 4;
+    *out = hold.release();
+    return BSK_OK;
+}
+
+extern "C" int bsk_index_info(const bsk_index *ix, uint64_t *n_targets, uint64_t *n_postings, uint64_t *n_distinct, uint64_t *max_bucket,
+                              uint64_t *device_bytes) {
+    if (!ix) return BSK_ERR_ARG;
+    if (n_targets) *n_targets = ix->n_targets;
+    if (n_postings) *n_postings = ix->n_postings;
+    if (n_distinct) *n_distinct = ix->n_distinct;
+    if (max_bucket) *max_bucket = ix->max_bucket;
+    if (device_bytes) *device_bytes = ix->device_bytes;
+    return BSK_OK;
+}
+
+extern "C" void bsk_hits_release(bsk_hits *h) {
+    if (!h) return;
+    if (h->ctx) (void)hipSetDevice(h->ctx->device);
+    (void)hipFree(h->offsets);
+    (void)hipFree(h->target);
+    (void)hipFree(h->shared);
+    delete h;
+}
+
+static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, const bsk_search_params *sp, bsk_hits *res);
+extern "C" int bsk_index_search(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *queries, const bsk_search_params *sp, bsk_hits **hits) {
+    if (!ctx || !ix || !queries || !sp || !hits) return fail_arg(ctx, "bsk_index_search: null argument");
+    if (ix->ctx != ctx || queries->ctx != ctx || (*hits && (*hits)->ctx != ctx))
+        return fail_arg(ctx, "bsk_index_search: the index, the queries or the hits belong to another context");
+    if (sp->reserved != 0) return fail_arg(ctx, "bsk_index_search: reserved != 0");
+    if (!(sp->min_query_cov >= 0.0 && sp->min_query_cov <= 1.0) || !(sp->min_target_cov >= 0.0 && sp->min_target_cov <= 1.0))
+        return fail_arg(ctx, "bsk_index_search: a cover outside 0..1 (or NaN)");
+    if (queries->n_sets >= (1ULL << 32) || queries->n_values >= (1ULL << 32)) {
+        ctx->err = "bsk_index_search: 2^32 query sets or query values or more (split the queries)";
+        return BSK_ERR_UNSUPPORTED;
+    }
+    bsk_hits *res = *hits;
+    *hits = nullptr;
+    if (!res) res = new (std::nothrow) bsk_hits();
+    if (!res) return BSK_ERR_NOMEM;
+    res->ctx = ctx;
+    const int rc = search_impl(ctx, ix, queries, sp, res);
+    if (rc != BSK_OK) {
+        bsk_hits_release(res);
+        return rc;
+    }
+    *hits = res;
+    return BSK_OK;
+}
+
+static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, const bsk_search_params *sp, bsk_hits *res) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const u64 nq = qs->n_sets, nv = qs->n_values, T = ix->n_targets;
+    const Thr thr{sp->min_shared ? sp->min_shared : 1u, sp->min_query_cov, sp->min_target_cov};
+    auto grow = [&](void **p, size_t *cap, size_t bytes) -> hipError_t {  // the hits' own arrays: grow-only
+        if (*cap >= bytes && *p) return hipSuccess;
+        (void)hipFree(*p);
+        *p = nullptr;
+        *cap = 0;
+        const size_t want = bytes + bytes / 4 + 256;
+        const hipError_t e = hipMalloc(p, want);
+        if (e == hipSuccess) *cap = want;
+        return e;
+    };
+    res->n_queries = nq;
+    res->n_hits = 0;
+    res->n_large = 0;
+    HIPCHK(ctx, grow((void **)&res->offsets, &res->c_offsets, (nq + 1) * 8));
+    // per-query arrays (slot 10) and the query values' posting ranges (slot 11)
+    Carve cq;
+    const size_t o_qsum = cq.add<u64>(nq), o_stage = cq.add<u64>(nq + 1), o_hcnt = cq.add<u64>(nq), o_lslot = cq.add<u64>(nq + 1),
+                 o_loff = cq.add<u64>(nq + 1), o_part = cq.add<u64>((nq + SCAN_CHUNK - 1) / SCAN_CHUNK + 2), o_tot = cq.add<u64>(8),
+                 o_lq = cq.add<u32>(nq);
+    void *bq = nullptr, *brng = nullptr;
+    HIPCHK(ctx, pool_get(ctx, 10, cq.bytes, &bq));
+    HIPCHK(ctx, pool_get(ctx, 11, (nv ? nv : 1) * 8, &brng));
+    u64 *qsum = at<u64>(bq, o_qsum), *stage_off = at<u64>(bq, o_stage), *hcnt = at<u64>(bq, o_hcnt), *lslot = at<u64>(bq, o_lslot),
+        *loff = at<u64>(bq, o_loff), *part = at<u64>(bq, o_part), *tot = at<u64>(bq, o_tot), *rng = static_cast<u64 *>(brng);
+    u32 *lq = at<u32>(bq, o_lq);
+    HIPCHK(ctx, hipMemsetAsync(tot, 0, 64, st));  // [0] staging, [1] large target ids, [2] large queries, [3] large runs, [4] kept runs, [5] hits
+    // A. lookups
+    if (nq) {
+        hipLaunchKernelGGL(k_sr_lookup, dim3(grid_for(ctx, nq * 16, 256, 32)), dim3(256), 0, st, qs->offsets, qs->values, nq, ix->keys, ix->post_off, ix->dir,
+                           ix->bits, rng, qsum);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    // B. staging spans, the large queries' slots and target-id offsets
+    HIPCHK(ctx, scan_counts(st, StageOf{qsum, T}, nq, part, stage_off, tot + 0, (u64 *)nullptr));
+    HIPCHK(ctx, scan_counts(st, LargeOf{qsum, false}, nq, part, loff, tot + 1, (u64 *)nullptr));
+    HIPCHK(ctx, scan_counts(st, LargeOf{qsum, true}, nq, part, lslot, tot + 2, (u64 *)nullptr));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 24, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const u64 S = ctx->h_pinned[0], L = ctx->h_pinned[1], NL = ctx->h_pinned[2];
+    void *bst = nullptr;
+    HIPCHK(ctx, pool_get(ctx, 15, (S ? S : 1) * 8, &bst));
+    u32 *st_tgt = static_cast<u32 *>(bst), *st_sh = st_tgt + (S ? S : 1);
+    // C. queries of at most SR_CAP target ids
+    if (nq) {
+        hipLaunchKernelGGL(k_sr_small, dim3(grid_for(ctx, nq, SR_WAVES, 40)), dim3(64 * SR_WAVES), 0, st, qs->offsets, rng, qsum, nq, ix->post_tgt, ix->tsize,
+                           stage_off, thr, st_tgt, st_sh, hcnt);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    // the large path
+    if (NL) {
+        Carve cl;
+        const size_t o_in = cl.add<u64>(L + 1), o_out = cl.add<u64>(L), o_rstart = cl.add<u64>(L + 1), o_kpos = cl.add<u64>(L + 1),
+                     o_flag = cl.add<u32>(L), o_sfirst = cl.add<u64>(NL), o_part2 = cl.add<u64>((L + SCAN_CHUNK - 1) / SCAN_CHUNK + 2);
+        void *bl = nullptr;
+        HIPCHK(ctx, pool_get(ctx, 30, cl.bytes, &bl));
+        u64 *lin = at<u64>(bl, o_in), *lout = at<u64>(bl, o_out), *rstart = at<u64>(bl, o_rstart), *kpos = at<u64>(bl, o_kpos), *sfirst = at<u64>(bl, o_sfirst),
+            *part2 = at<u64>(bl, o_part2);
+        u32 *flag = at<u32>(bl, o_flag);
+        hipLaunchKernelGGL(k_sr_list_large, dim3(grid_for(ctx, nq, 256, 8)), dim3(256), 0, st, qsum, nq, lslot, lq);
+        hipLaunchKernelGGL(k_lg_emit, dim3(grid_for(ctx, NL, 4, 16)), dim3(256), 0, st, qs->offsets, rng, lq, NL, loff, ix->post_tgt, lin);
+        HIPCHK(ctx, hipGetLastError());
+        const unsigned end_bit = 32 + (NL > 1 ? 64 - __builtin_clzll(NL - 1) : 0);
+        size_t tb = 0;
+        HIPCHK(ctx, sets_sort_u64(nullptr, tb, lin, lout, (size_t)L, 0, end_bit, st));
+        void *stmp = nullptr;
+        HIPCHK(ctx, pool_get(ctx, 31, tb ? tb : 8, &stmp));
+        HIPCHK(ctx, sets_sort_u64(stmp, tb, lin, lout, (size_t)L, 0, end_bit, st));
+        u64 *ridx = lin;  // (free after the sort; L + 1 entries)
+        hipLaunchKernelGGL(k_run_heads, dim3(grid_for(ctx, L, 256, 16)), dim3(256), 0, st, lout, L, flag);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, scan_counts(st, KeepOf{flag}, L, part2, ridx, tot + 3, (u64 *)nullptr));
+        hipLaunchKernelGGL(k_lg_runs, dim3(grid_for(ctx, L, 256, 16)), dim3(256), 0, st, flag, ridx, L, rstart);
+        u32 *keep = flag;  // (free once the runs are known)
+        hipLaunchKernelGGL(k_lg_keep, dim3(grid_for(ctx, L, 256, 16)), dim3(256), 0, st, lout, rstart, ridx, L, lq, qs->offsets, ix->tsize, thr, keep, sfirst);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, scan_counts(st, KeepOf{keep}, L, part2, kpos, tot + 4, (u64 *)nullptr));
+        hipLaunchKernelGGL(k_lg_place, dim3(grid_for(ctx, L, 256, 16)), dim3(256), 0, st, lout, rstart, ridx, L, keep, kpos, sfirst, lq, stage_off, st_tgt, st_sh,
+                           hcnt);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    // hit offsets, then the move out of the staging spans
+    HIPCHK(ctx, scan_counts(st, ArrayOf{hcnt}, nq, part, res->offsets, tot + 5, (u64 *)nullptr));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot + 5, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const u64 H = ctx->h_pinned[0];
+    HIPCHK(ctx, grow((void **)&res->target, &res->c_target, (H ? H : 1) * 4));
+    HIPCHK(ctx, grow((void **)&res->shared, &res->c_shared, (H ? H : 1) * 4));
+    if (H) {
+        hipLaunchKernelGGL(k_sr_move, dim3(grid_for(ctx, nq * 16, 256, 32)), dim3(256), 0, st, stage_off, res->offsets, hcnt, nq, st_tgt, st_sh, res->target,
+                           res->shared);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    res->n_hits = H;
+    res->n_large = NL;
+    snprintf(res->plan, sizeof res->plan, "k_sr_lookup + k_sr_small (LDS sort, <= %d target ids per query); large path: %llu queries, %llu target ids",
+             SR_CAP, (unsigned long long)NL, (unsigned long long)L);
+    return BSK_OK;
+}
+
+extern "C" int bsk_hits_info(const bsk_hits *h, uint64_t *n_queries, uint64_t *n_hits) {
+    if (!h) return BSK_ERR_ARG;
+    if (n_queries) *n_queries = h->n_queries;
+    if (n_hits) *n_hits = h->n_hits;
+    return BSK_OK;
+}
+
+extern "C" int bsk_hits_plan(const bsk_hits *h, const char **plan, uint64_t *n_large_queries) {
+    if (!h) return BSK_ERR_ARG;
+    if (plan) *plan = h->plan;
+    if (n_large_queries) *n_large_queries = h->n_large;
+    return BSK_OK;
+}
+
+extern "C" int bsk_hits_device(const bsk_hits *h, const uint64_t **offsets, const uint32_t **target, const uint32_t **shared) {
+    if (!h) return BSK_ERR_ARG;
+    if (offsets) *offsets = (const uint64_t *)h->offsets;
+    if (target) *target = (const uint32_t *)h->target;
+    if (shared) *shared = (const uint32_t *)h->shared;
+    return BSK_OK;
+}
+
+extern "C" int bsk_hits_fetch(bsk_ctx *ctx, const bsk_hits *h, uint64_t first, uint64_t count, uint64_t *offsets, uint32_t *target, uint32_t *shared,
+                              uint64_t hit_cap) {
+    if (!ctx || !h || !offsets) return fail_arg(ctx, "bsk_hits_fetch: null argument");
+    if (h->ctx != ctx) return fail_arg(ctx, "bsk_hits_fetch: the hits belong to another context");
+    if (first > h->n_queries || count > h->n_queries - first) return fail_arg(ctx, "bsk_hits_fetch: range outside the hits");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<u64> o(count + 1);
+    HIPCHK(ctx, hipMemcpyAsync(o.data(), h->offsets + first, (count + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const u64 nh = o[count] - o[0];
+    for (u64 i = 0; i <= count; ++i) offsets[i] = o[i] - o[0];
+    if (!target && !shared) return BSK_OK;
+    if (nh > hit_cap) return fail_arg(ctx, "bsk_hits_fetch: hit_cap too small");
+    if (nh && target) HIPCHK(ctx, hipMemcpyAsync(target, h->target + o[0], nh * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (nh && shared) HIPCHK(ctx, hipMemcpyAsync(shared, h->shared + o[0], nh * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return BSK_OK;
+}

@@ -19,14 +19,7 @@
 
 #include "biosketch.h"
 #include "host_types.hpp"
-
-struct bsk_sets {
-    bsk_ctx *ctx = nullptr;
-    u64 n_sets = 0, n_values = 0;
-    u64 *offsets = nullptr;  // [n_sets + 1]
-    u64 *values = nullptr;   // [n_values] ascending inside a set
-    size_t c_offsets = 0, c_values = 0;  // bytes allocated (grow-only when the object is re-used: bsk_result_sets_reuse)
-};
+#include "sets_internal.hpp"
 
 namespace {
 
@@ -229,8 +222,6 @@ __global__ __launch_bounds__(256) void k_sets_rows(const u64 *hash, const u64 *r
     }
 }
 
-// ---- exclusive scan of n per-sequence numbers (counts taken from the result's reference words, or an array) into out[0 .. n]
-// (out[n] = the total); three small kernels: block sums, one block over the block sums, local scan + block offset ----
 struct CountOf {
     const u64 *refs, *wfirst, *wcount;
     __device__ __forceinline__ u64 operator()(u64 r) const {
@@ -239,115 +230,6 @@ struct CountOf {
         return c;
     }
 };
-struct ArrayOf {
-    const u64 *a;
-    __device__ __forceinline__ u64 operator()(u64 r) const { return a[r]; }
-};
-struct KeepOf {
-    const u32 *a;
-    __device__ __forceinline__ u64 operator()(u64 r) const { return (u64)a[r]; }
-};
-#define SCAN_PER_THREAD 8
-#define SCAN_BLOCK 256
-#define SCAN_CHUNK (SCAN_PER_THREAD * SCAN_BLOCK)
-__device__ __forceinline__ u64 wave_incl(u64 x, int lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 t = __shfl_up(x, d, 64);
-        if (lane >= d) x += t;
-    }
-    return x;
-}
-template <class F>
-__global__ __launch_bounds__(SCAN_BLOCK) void k_scan_sums(F f, u64 n, u64 *part, u64 *mx) {
-    __shared__ u64 s_w[SCAN_BLOCK / 64];
-    const u64 b0 = (u64)blockIdx.x * SCAN_CHUNK;
-    u64 sum = 0, m = 0, x[SCAN_PER_THREAD];
-#pragma unroll
-    for (int i = 0; i < SCAN_PER_THREAD; ++i) {  // all loads in flight before the first use
-        const u64 r = b0 + (u64)i * SCAN_BLOCK + threadIdx.x;
-        x[i] = r < n ? f(r) : 0;
-    }
-#pragma unroll
-    for (int i = 0; i < SCAN_PER_THREAD; ++i) {
-        sum += x[i];
-        m = x[i] > m ? x[i] : m;
-    }
-    for (int d = 32; d; d >>= 1) {
-        sum += __shfl_xor(sum, d, 64);
-        const u64 t = __shfl_xor(m, d, 64);
-        m = t > m ? t : m;
-    }
-    __shared__ u64 s_m[SCAN_BLOCK / 64];
-    if ((threadIdx.x & 63) == 0) {
-        s_w[threadIdx.x >> 6] = sum;
-        s_m[threadIdx.x >> 6] = m;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 t = 0, bm = 0;
-        for (int w = 0; w < SCAN_BLOCK / 64; ++w) {
-            t += s_w[w];
-            bm = s_m[w] > bm ? s_m[w] : bm;
-        }
-        part[blockIdx.x] = t;
-        // one atomic per block, and only when it can raise the maximum (thousands of blocks hitting one address serialise in the L2)
-        if (mx && bm > __hip_atomic_load(mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax((unsigned long long *)mx, (unsigned long long)bm);
-    }
-}
-__global__ __launch_bounds__(1024) void k_scan_top(u64 *part, u64 nb, u64 *total) {  // in place: part[b] <- sum of part[0 .. b)
-    __shared__ u64 s_w[16];
-    __shared__ u64 s_carry;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (u64 b0 = 0; b0 < nb; b0 += 1024) {
-        const u64 i = b0 + threadIdx.x;
-        const u64 x = i < nb ? part[i] : 0;
-        const u64 inc = wave_incl(x, lane);
-        if (lane == 63) s_w[w] = inc;
-        __syncthreads();
-        u64 before = s_carry;
-        for (int q = 0; q < w; ++q) before += s_w[q];
-        if (i < nb) part[i] = before + inc - x;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = before + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = s_carry;
-}
-template <class F>
-__global__ __launch_bounds__(SCAN_BLOCK) void k_scan_apply(F f, u64 n, const u64 *part, const u64 *total, u64 *out) {
-    __shared__ u64 s_w[SCAN_BLOCK / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    // thread t owns SCAN_PER_THREAD consecutive numbers
-    const u64 r0 = (u64)blockIdx.x * SCAN_CHUNK + (u64)threadIdx.x * SCAN_PER_THREAD;
-    u64 x[SCAN_PER_THREAD], sum = 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_PER_THREAD; ++i) x[i] = r0 + i < n ? f(r0 + i) : 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_PER_THREAD; ++i) sum += x[i];
-    const u64 inc = wave_incl(sum, lane);
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    u64 run = part[blockIdx.x] + inc - sum;
-    for (int q = 0; q < w; ++q) run += s_w[q];
-#pragma unroll
-    for (int i = 0; i < SCAN_PER_THREAD; ++i) {
-        if (r0 + i < n) out[r0 + i] = run;
-        run += x[i];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = *total;
-}
-// out[0..n] = exclusive scan of f(0..n-1); *total_dev (device) receives the total, *mx_dev (may be NULL) the maximum
-template <class F>
-hipError_t scan_counts(hipStream_t st, F f, u64 n, u64 *part, u64 *out, u64 *total_dev, u64 *mx_dev) {
-    const u64 nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    if (nb) hipLaunchKernelGGL(k_scan_sums<F>, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, st, f, n, part, mx_dev);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, st, part, nb, total_dev);
-    if (nb) hipLaunchKernelGGL(k_scan_apply<F>, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, st, f, n, part, total_dev, out);
-    else hipLaunchKernelGGL(k_scan_apply<F>, dim3(1), dim3(SCAN_BLOCK), 0, st, f, n, part, total_dev, out);
-    return hipGetLastError();
-}
 
 // final placement: sequence r's run [in_off[r], +ucount[r]) -> [out_off[r], ...); a group of 32 lanes per sequence
 __global__ void k_move_seqs(const u64 *tmp, const u64 *in_off, const u64 *out_off, const u64 *ucount, u64 n, u64 *out) {
@@ -875,6 +757,10 @@ static int sets_impl(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bs
 #undef SCHK
     *out = res;
     return done(BSK_OK);
+}
+
+hipError_t sets_sort_u64(void *tmp, size_t &tmp_bytes, u64 *in, u64 *out, size_t n, unsigned begin_bit, unsigned end_bit, hipStream_t st) {
+    return rocprim::radix_sort_keys(tmp, tmp_bytes, in, out, n, begin_bit, end_bit, st);
 }
 
 extern "C" int bsk_sets_info(const bsk_sets *s, uint64_t *n_sets, uint64_t *n_values) {

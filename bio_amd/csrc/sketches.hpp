@@ -141,9 +141,92 @@ class Engine {
         return rc;
     }
     const char *last_error() const { return bsk_last_error(ctx_); }
+    bsk_ctx *ctx() const { return ctx_; }  // for the C entries without a mirror here
 
    private:
     bsk_ctx *ctx_ = nullptr;
+};
+
+// ---- containment search (include/biosketch.h): RAII owners of the device objects ----
+template <class T, void (*Release)(T *)>
+class Owned {
+   public:
+    Owned() = default;
+    ~Owned() { Release(p_); }
+    Owned(Owned &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    Owned &operator=(Owned &&o) noexcept {
+        if (this != &o) {
+            Release(p_);
+            p_ = o.p_;
+            o.p_ = nullptr;
+        }
+        return *this;
+    }
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    T *get() const { return p_; }
+    T *&handle() { return p_; }  // in-out slot for the C entries (release before overwriting, or pass for re-use)
+
+   protected:
+    T *p_ = nullptr;
+};
+
+// sorted distinct value sets on the device (bsk_sets)
+class DeviceSets : public Owned<bsk_sets, bsk_sets_release> {
+   public:
+    // offsets[n+1] (offsets[0] = 0, offsets[n] = values.size()), values strictly ascending inside a set
+    int from_host(Engine &e, const std::vector<uint64_t> &offsets, const std::vector<uint64_t> &values) {
+        if (offsets.empty() || offsets.back() != values.size()) return BSK_ERR_ARG;
+        bsk_sets_release(p_);
+        p_ = nullptr;
+        return bsk_sets_from_host(e.ctx(), offsets.data(), offsets.size() - 1, values.empty() ? nullptr : values.data(), &p_);
+    }
+    uint64_t n_sets() const {
+        uint64_t n = 0;
+        bsk_sets_info(p_, &n, nullptr);
+        return n;
+    }
+};
+
+// hits of a search (bsk_hits): CSR by query, target ids ascending inside a query
+class SearchHits : public Owned<bsk_hits, bsk_hits_release> {
+   public:
+    int fetch(Engine &e, std::vector<uint64_t> &offsets, std::vector<uint32_t> &target, std::vector<uint32_t> &shared) const {
+        uint64_t nq = 0, nh = 0;
+        int rc = bsk_hits_info(p_, &nq, &nh);
+        if (rc != BSK_OK) return rc;
+        offsets.assign(nq + 1, 0);
+        target.assign(nh + 1, 0);
+        shared.assign(nh + 1, 0);
+        rc = bsk_hits_fetch(e.ctx(), p_, 0, nq, offsets.data(), target.data(), shared.data(), nh + 1);
+        target.resize(nh);
+        shared.resize(nh);
+        return rc;
+    }
+    uint64_t large_queries() const {
+        uint64_t n = 0;
+        bsk_hits_plan(p_, nullptr, &n);
+        return n;
+    }
+};
+
+// inverted index of target sets (bsk_index)
+class SearchIndex : public Owned<bsk_index, bsk_index_release> {
+   public:
+    int build(Engine &e, const DeviceSets &targets) {
+        bsk_index_release(p_);
+        p_ = nullptr;
+        return bsk_index_build(e.ctx(), targets.get(), &p_);
+    }
+    // into: empty, or the hits of an earlier search on this engine (its device arrays are kept and only grow)
+    int search(Engine &e, const DeviceSets &queries, const bsk_search_params &sp, SearchHits &into) const {
+        return bsk_index_search(e.ctx(), p_, queries.get(), &sp, &into.handle());
+    }
+    uint64_t max_bucket() const {
+        uint64_t m = 0;
+        bsk_index_info(p_, nullptr, nullptr, nullptr, &m, nullptr);
+        return m;
+    }
 };
 
 inline Engine &default_engine() {

@@ -204,6 +204,14 @@ class BatchResult:
         finally:
             self.eng.lib.bsk_sets_release(h)
 
+    def device_sets(self, whole_batch: bool = False, scale: int = 1) -> "Sets":
+        """The same sets as sets(), left ON THE DEVICE (bsk_result_sets) -> Sets: index them or search them without a round trip."""
+        h = C.c_void_p()
+        self.eng._opts()
+        self.eng._chk(self.eng.lib.bsk_result_sets(self.eng.ctx, self.h, L.SETS_WHOLE_BATCH if whole_batch else L.SETS_PER_SEQUENCE, scale,
+                                                   C.byref(h)))
+        return Sets(self.eng, h)
+
     def compact(self):
         """bsk_result_compact: dense CSR copy left ON THE DEVICE -> (offsets_ptr, hash_ptr, pos_ptr or None, n_tuples); the arrays belong
         to the engine's context until its next compact()."""
@@ -233,6 +241,180 @@ class BatchResult:
     def close(self):
         if self.h:
             self.eng.lib.bsk_result_release(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Sets:
+    """Device-resident sorted distinct value sets (bsk_sets): offsets[n_sets+1] and values[] stay on the device until close()."""
+
+    def __init__(self, eng: "Engine", handle):
+        self.eng, self.h = eng, handle
+
+    def info(self):
+        ns, nv = C.c_uint64(), C.c_uint64()
+        self.eng._chk(self.eng.lib.bsk_sets_info(self.h, C.byref(ns), C.byref(nv)))
+        return dict(n_sets=ns.value, n_values=nv.value)
+
+    def offsets(self) -> np.ndarray:
+        """offsets[n_sets+1] to the host (the sets' sizes are its differences)"""
+        ns = self.info()["n_sets"]
+        offs = np.zeros(ns + 1, np.uint64)
+        self.eng._chk(self.eng.lib.bsk_sets_fetch(self.eng.ctx, self.h, 0, ns, offs.ctypes.data, None, 0))
+        return offs
+
+    def fetch(self):
+        """bsk_sets_fetch -> (offsets[n_sets+1], values)"""
+        inf = self.info()
+        offs = np.zeros(inf["n_sets"] + 1, np.uint64)
+        vals = np.zeros(max(inf["n_values"], 1), np.uint64)
+        self.eng._chk(self.eng.lib.bsk_sets_fetch(self.eng.ctx, self.h, 0, inf["n_sets"], offs.ctypes.data, vals.ctypes.data, vals.size))
+        return offs, vals[: inf["n_values"]]
+
+    def device(self):
+        """bsk_sets_device -> (offsets_ptr, values_ptr)"""
+        po, pv = C.c_void_p(), C.c_void_p()
+        self.eng._chk(self.eng.lib.bsk_sets_device(self.h, C.byref(po), C.byref(pv)))
+        return po.value, pv.value
+
+    def index(self) -> "Index":
+        """Inverted index of these sets as search targets (bsk_index_build); the sets may be closed afterwards."""
+        h = C.c_void_p()
+        self.eng._chk(self.eng.lib.bsk_index_build(self.eng.ctx, self.h, C.byref(h)))
+        return Index(self.eng, h, np.diff(self.offsets()))
+
+    def close(self):
+        if self.h:
+            self.eng.lib.bsk_sets_release(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Index:
+    """Device-resident inverted index of target sets (bsk_index): value -> ascending target ids."""
+
+    def __init__(self, eng: "Engine", handle, target_sizes: np.ndarray):
+        self.eng, self.h = eng, handle
+        self.target_sizes = np.asarray(target_sizes, np.uint64)
+
+    def info(self):
+        v = [C.c_uint64() for _ in range(5)]
+        self.eng._chk(self.eng.lib.bsk_index_info(self.h, *[C.byref(x) for x in v]))
+        return dict(n_targets=v[0].value, n_postings=v[1].value, n_distinct=v[2].value, max_bucket=v[3].value, device_bytes=v[4].value)
+
+    def search(self, queries: Sets, min_shared: int = 1, min_query_cov: float = 0.0, min_target_cov: float = 0.0,
+               reuse: Optional["Hits"] = None) -> "Hits":
+        """Every (query, target) pair that shares s values with s >= max(min_shared, 1), s >= min_query_cov * |q| and
+        s >= min_target_cov * |t| (bsk_index_search).  reuse: the Hits of an earlier search, whose device arrays are kept."""
+        sp = L.SearchParams(min_shared, 0, min_query_cov, min_target_cov)
+        h = reuse.h if reuse is not None and reuse.h else C.c_void_p()
+        rc = self.eng.lib.bsk_index_search(self.eng.ctx, self.h, queries.h, C.byref(sp), C.byref(h))
+        if reuse is not None:
+            reuse.h = h if h.value else None  # (kept on an argument error, released by the library on any other)
+        self.eng._chk(rc)
+        res = reuse if reuse is not None else Hits(self.eng)
+        res._bind(h, np.diff(queries.offsets()), self.target_sizes)
+        return res
+
+    def close(self):
+        if self.h:
+            self.eng.lib.bsk_index_release(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Hits:
+    """CSR hits of one search (bsk_hits): offsets[n_queries+1], target[] ascending inside a query, shared[]; fetched on first use."""
+
+    def __init__(self, eng: "Engine"):
+        self.eng, self.h = eng, None
+        self._host = None
+
+    def _bind(self, h, query_sizes: np.ndarray, target_sizes: np.ndarray):
+        self.h, self._host = h, None
+        self.query_sizes, self.target_sizes = query_sizes.astype(np.uint64), target_sizes
+
+    def info(self):
+        nq, nh = C.c_uint64(), C.c_uint64()
+        self.eng._chk(self.eng.lib.bsk_hits_info(self.h, C.byref(nq), C.byref(nh)))
+        return dict(n_queries=nq.value, n_hits=nh.value)
+
+    def plan(self):
+        """What the search ran (bsk_hits_plan): a description and how many queries took the large-query (sort) path."""
+        p, n = C.c_char_p(), C.c_uint64()
+        self.eng._chk(self.eng.lib.bsk_hits_plan(self.h, C.byref(p), C.byref(n)))
+        return dict(plan=(p.value or b"").decode(), n_large_queries=n.value)
+
+    def device(self):
+        """bsk_hits_device -> (offsets_ptr, target_ptr, shared_ptr)"""
+        po, pt, ps = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.eng._chk(self.eng.lib.bsk_hits_device(self.h, C.byref(po), C.byref(pt), C.byref(ps)))
+        return po.value, pt.value, ps.value
+
+    def fetch(self, first: int = 0, count: Optional[int] = None):
+        """bsk_hits_fetch -> (offsets[count+1] rebased, target[], shared[])"""
+        inf = self.info()
+        if count is None:
+            count = inf["n_queries"] - first
+        offs = np.zeros(count + 1, np.uint64)
+        self.eng._chk(self.eng.lib.bsk_hits_fetch(self.eng.ctx, self.h, first, count, offs.ctypes.data, None, None, 0))
+        n = int(offs[-1])
+        tgt = np.zeros(max(n, 1), np.uint32)
+        sh = np.zeros(max(n, 1), np.uint32)
+        self.eng._chk(self.eng.lib.bsk_hits_fetch(self.eng.ctx, self.h, first, count, offs.ctypes.data, tgt.ctypes.data, sh.ctypes.data, tgt.size))
+        return offs, tgt[:n], sh[:n]
+
+    def _cache(self):
+        if self._host is None:
+            self._host = self.fetch()
+        return self._host
+
+    @property
+    def offsets(self) -> np.ndarray:
+        return self._cache()[0]
+
+    @property
+    def target(self) -> np.ndarray:
+        return self._cache()[1]
+
+    @property
+    def shared(self) -> np.ndarray:
+        return self._cache()[2]
+
+    def query(self) -> np.ndarray:
+        """the query index of every hit"""
+        return np.repeat(np.arange(len(self.offsets) - 1, dtype=np.uint64), np.diff(self.offsets).astype(np.int64))
+
+    def containment(self) -> np.ndarray:
+        """shared / |q| per hit"""
+        q = self.query_sizes[self.query().astype(np.int64)].astype(np.float64)
+        return self.shared.astype(np.float64) / q
+
+    def jaccard(self) -> np.ndarray:
+        """shared / (|q| + |t| - shared) per hit"""
+        s = self.shared.astype(np.float64)
+        q = self.query_sizes[self.query().astype(np.int64)].astype(np.float64)
+        t = self.target_sizes[self.target.astype(np.int64)].astype(np.float64)
+        return s / (q + t - s)
+
+    def close(self):
+        if self.h:
+            self.eng.lib.bsk_hits_release(self.h)
             self.h = None
 
     def __del__(self):
@@ -392,6 +574,18 @@ class Engine:
         self._chk(self.lib.bsk_batch_from_ascii(self.ctx, data.ctypes.data, offsets.ctypes.data, len(offsets) - 1,
                                                 alphabet, C.byref(h)))
         return Batch(self, h)
+
+    def sets_from_arrays(self, offsets: np.ndarray, values: np.ndarray) -> Sets:
+        """Sets from the host (bsk_sets_from_host): offsets[n_sets+1] (offsets[0] = 0, offsets[-1] = len(values)), values strictly
+        ascending inside every set -- e.g. a reference collection loaded from disk."""
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        values = np.ascontiguousarray(values, np.uint64)
+        if offsets.ndim != 1 or len(offsets) < 1 or int(offsets[-1]) != len(values):
+            raise ValueError("sets_from_arrays: offsets must have n_sets + 1 entries and end at len(values)")
+        h = C.c_void_p()
+        self._chk(self.lib.bsk_sets_from_host(self.ctx, offsets.ctypes.data, len(offsets) - 1, values.ctypes.data if len(values) else None,
+                                              C.byref(h)))
+        return Sets(self, h)
 
     def batch_from_packed(self, words: np.ndarray, desc: np.ndarray) -> Batch:
         words = np.ascontiguousarray(words, np.uint32)

@@ -478,6 +478,52 @@ int bsk_sets_fetch(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t cou
 int bsk_sets_device(const bsk_sets *s, const uint64_t **offsets, const uint64_t **values);
 void bsk_sets_release(bsk_sets *s);
 
+/* ---- containment search of sets against a device-resident index ----------------------------------------------------
+ * What a kmcp-style consumer does with the sets: for every query set (a read, a genome), which target sets share how many values
+ * with it -- containment shared / |q|, Jaccard shared / (|q| + |t| - shared) -- computed where the sets already are.
+ *
+ * Sets from the host (e.g. a reference collection loaded from disk): offsets[n_sets+1] (offsets[0] = 0, non-decreasing),
+ * values[offsets[n_sets]], strictly ascending inside every set -- anything else is BSK_ERR_ARG (checked; nothing is kept on error).
+ * Any u64 is a legal value, 0 and 2^64-1 included.  The result is an ordinary bsk_sets of ctx: bsk_sets_info / _fetch / _device /
+ * _release work on it.  Host pointers are not retained. */
+int bsk_sets_from_host(bsk_ctx *ctx, const uint64_t *offsets, uint64_t n_sets, const uint64_t *values, bsk_sets **out);
+
+/* Inverted index of a collection of target sets: value -> ascending list of the targets that hold it.  It owns copies of everything
+ * it needs (the target sets' sizes included), so the bsk_sets may be released after the build.  Layout: the values pass a bijective
+ * 64-bit mixer (the splitmix64 finalizer), the distinct mixed keys are sorted, each with its posting list of target ids (u32), and a
+ * directory over the top b bits of the mixed key (2^b <= distinct keys < 2^(b+1)) points into the keys: a lookup reads one
+ * directory entry and a bucket of one or two keys.  Fewer than 2^32 targets and fewer than 2^32 postings (values over all targets),
+ * else BSK_ERR_UNSUPPORTED.  max_bucket: the most keys one directory bucket holds. */
+typedef struct bsk_index bsk_index;
+int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index **out);
+int bsk_index_info(const bsk_index *ix, uint64_t *n_targets, uint64_t *n_postings, uint64_t *n_distinct, uint64_t *max_bucket,
+                   uint64_t *device_bytes); /* any out-pointer may be NULL */
+void bsk_index_release(bsk_index *ix);
+
+typedef struct bsk_search_params {
+    uint32_t min_shared;    /* 0 is taken as 1: a pair that shares nothing is never listed */
+    uint32_t reserved;      /* 0 */
+    double min_query_cov;   /* 0..1 */
+    double min_target_cov;  /* 0..1 */
+} bsk_search_params;
+/* For every query set q and target t with s = |q & t|: the pair is listed iff
+ *   s >= max(min_shared, 1)  &&  (double)s >= min_query_cov * (double)|q|  &&  (double)s >= min_target_cov * (double)|t|
+ * (IEEE double, exactly this expression).  Hits are CSR by query: offsets[n_queries+1] (u64), target[] (u32) ascending inside a
+ * query, shared[] (u32).  *hits may be NULL (new object) or the object of an earlier search on this context: its device arrays are
+ * kept and only grow (as bsk_result_sets_reuse); an argument error leaves *hits as it was, any other error releases it and sets
+ * *hits to NULL.  queries and ix must belong to ctx.
+ * Everything runs on the context's stream; the host reads back sizes only.  A query whose posting lists hold more target ids than
+ * one wavefront's LDS budget takes an exact sort-based path instead (bsk_hits_plan counts them). */
+typedef struct bsk_hits bsk_hits;
+int bsk_index_search(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *queries, const bsk_search_params *sp, bsk_hits **hits);
+int bsk_hits_info(const bsk_hits *h, uint64_t *n_queries, uint64_t *n_hits);
+/* what the last search into h ran: a short description, and how many queries took the large-query path (either may be NULL) */
+int bsk_hits_plan(const bsk_hits *h, const char **plan, uint64_t *n_large_queries);
+int bsk_hits_fetch(bsk_ctx *ctx, const bsk_hits *h, uint64_t first, uint64_t count, uint64_t *offsets /* rebased */, uint32_t *target,
+                   uint32_t *shared, uint64_t hit_cap);
+int bsk_hits_device(const bsk_hits *h, const uint64_t **offsets, const uint32_t **target, const uint32_t **shared);
+void bsk_hits_release(bsk_hits *h);
+
 #ifdef __cplusplus
 }
 #endif
