@@ -8,7 +8,7 @@
 // clustered: a directory over raw top bits would put them all in bucket 0).  One rocprim::radix_sort_pairs<u64, u32> of
 // (key, target): the sort is stable and the input is target-major, so the targets of a key leave ascending.  Run-length of the keys
 // -> keys[U], post_off[U + 1], post_tgt[P]; a directory dir[2^b + 1] of bucket starts over the top b bits of the key, 2^b <= U <
-// 2^(b+1): one or two keys per bucket.
+// 2^(b+1): one or two keys per bucket on average (a lookup scans its whole bucket, however full).
 //
 // Search (bsk_index_search): A. lookups, a group of 16 lanes per query -- mix, one directory entry, a bucket scan -- store every
 // query value's posting range and the query's sum of posting lengths (coalesced); B. scans of those sums give every query a staging

@@ -491,9 +491,9 @@ int bsk_sets_from_host(bsk_ctx *ctx, const uint64_t *offsets, uint64_t n_sets, c
 /* Inverted index of a collection of target sets: value -> ascending list of the targets that hold it.  It owns copies of everything
  * it needs (the target sets' sizes included), so the bsk_sets may be released after the build.  Layout: the values pass a bijective
  * 64-bit mixer (the splitmix64 finalizer), the distinct mixed keys are sorted, each with its posting list of target ids (u32), and a
- * directory over the top b bits of the mixed key (2^b <= distinct keys < 2^(b+1)) points into the keys: a lookup reads one
- * directory entry and a bucket of one or two keys.  Fewer than 2^32 targets and fewer than 2^32 postings (values over all targets),
- * else BSK_ERR_UNSUPPORTED.  max_bucket: the most keys one directory bucket holds. */
+ * directory over the top b bits of the mixed key (2^b <= distinct keys < 2^(b+1)) points into the keys: a bucket holds one or two
+ * keys on average, and a lookup reads one directory entry and scans its whole bucket.  Fewer than 2^32 targets and fewer than
+ * 2^32 postings (values over all targets), else BSK_ERR_UNSUPPORTED.  max_bucket: the most keys one directory bucket holds. */
 typedef struct bsk_index bsk_index;
 int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index **out);
 int bsk_index_info(const bsk_index *ix, uint64_t *n_targets, uint64_t *n_postings, uint64_t *n_distinct, uint64_t *max_bucket,

@@ -1,47 +1,16 @@
 """GPU: containment search of sets against a device-resident index (bsk_sets_from_host, bsk_index_*, bsk_hits_*).
 
-Expected hits come from a plain NumPy reference: value -> targets, pairs counted, the contract's float64 threshold expression."""
+Expected hits come from a plain NumPy reference (tests/search_cases.py): value -> targets, pairs counted, the contract's float64
+threshold expression."""
 import numpy as np
 import pytest
 
 from bio_amd import _lib as L
 from bio_amd import sketches as S
+from tests.search_cases import collection, ref_search
 
 pytestmark = pytest.mark.gpu
 U64 = np.uint64
-
-
-def collection(sets):
-    """list of value arrays -> (offsets, values), every set sorted and distinct"""
-    sets = [np.unique(np.asarray(s, U64)) for s in sets]
-    offs = np.zeros(len(sets) + 1, U64)
-    offs[1:] = np.cumsum([len(s) for s in sets])
-    vals = np.concatenate(sets) if sets and offs[-1] else np.zeros(0, U64)
-    return offs, vals.astype(U64)
-
-
-def ref_search(t_offs, t_vals, q_offs, q_vals, min_shared=1, qc=0.0, tc=0.0):
-    """-> (offsets, target, shared) by the contract, computed on the host"""
-    nt, nq = len(t_offs) - 1, len(q_offs) - 1
-    tsz, qsz = np.diff(t_offs).astype(np.int64), np.diff(q_offs).astype(np.int64)
-    tid = np.repeat(np.arange(nt, dtype=U64), tsz)
-    order = np.argsort(t_vals, kind="stable")
-    sv, st = t_vals[order], tid[order]
-    qid = np.repeat(np.arange(nq, dtype=U64), qsz)
-    lo = np.searchsorted(sv, q_vals, "left")
-    cnt = np.searchsorted(sv, q_vals, "right") - lo
-    tot = int(cnt.sum())
-    starts = np.repeat(lo - (np.cumsum(cnt) - cnt), cnt) + np.arange(tot)
-    key = (np.repeat(qid, cnt) << U64(32)) | st[starts]
-    uk, c = np.unique(key, return_counts=True)
-    q, t = (uk >> U64(32)).astype(np.int64), (uk & U64(0xFFFFFFFF)).astype(np.int64)
-    c = c.astype(np.int64)
-    keep = (c >= max(min_shared, 1)) & (c.astype(np.float64) >= qc * qsz[q].astype(np.float64)) & \
-        (c.astype(np.float64) >= tc * tsz[t].astype(np.float64))
-    q, t, c = q[keep], t[keep], c[keep]
-    offs = np.zeros(nq + 1, U64)
-    offs[1:] = np.cumsum(np.bincount(q, minlength=nq))
-    return offs, t.astype(np.uint32), c.astype(np.uint32)
 
 
 def check(hits, want):
