@@ -122,8 +122,17 @@ __device__ __forceinline__ u64 pk_load_u64(const u64 *p) {
 // barrier for the arithmetic on its neighbours' results -- the address of the words was computed from the descriptor ahead of it).
 __device__ __forceinline__ void pk_wait_loads(u64 &d0, u64 &d1) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(d0), "+v"(d1)::"memory"); }
 __device__ __forceinline__ void pk_wait_loads(PkWords &p) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(p.a), "+v"(p.b), "+v"(p.c), "+v"(p.d)::"memory"); }
-__device__ __forceinline__ void pk_wait_loads(PkWords &p, u64 &d0, u32 &f) {
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(p.a), "+v"(p.b), "+v"(p.c), "+v"(p.d), "+v"(d0), "+v"(f)::"memory");
+// The returning ticket atomic from lane 0 alone, issued from inline asm like the loads above (the s_waitcnt pass would otherwise
+// wait for it at once): the caller takes its value at its next pk_wait_loads.  (+v: the lanes the atomic does not write keep their value.)
+__device__ __forceinline__ void pk_ticket_async(u32 *ticket, u32 &t) {
+    u64 ex;
+    asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, 1\n\tglobal_atomic_add %0, %2, %3, off sc0\n\ts_mov_b64 exec, %1"
+                 : "+v"(t), "=&s"(ex)
+                 : "v"(ticket), "v"(1u)
+                 : "memory");
+}
+__device__ __forceinline__ void pk_wait_loads(PkWords &p, u64 &d0, u32 &f, u32 &t) {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(p.a), "+v"(p.b), "+v"(p.c), "+v"(p.d), "+v"(d0), "+v"(f), "+v"(t)::"memory");
 }
 __device__ __forceinline__ u32 pk_load_u8(const u8 *p) {
     u32 r;
@@ -147,7 +156,7 @@ struct PkMin {
     u32 fl, fh_, rl, rh_;
     u32 S[W];   // packed suffix minima of the previous block (then raw packed values of the current one)
     u64 H[W];   // canonical hashes of the previous block, slot by slot replaced by the current block's
-    u32 SB[W];  // strand << 15 of the same slots
+    u32 SB[W];  // strand << 15 of the same slots (POS2: the whole staged u16 of the slot, 2 * position + strand)
     u32 P, bm, tmin;
     u32 nsel;  // SELM: the lane's selections so far
     u32 slot, spare;
@@ -161,6 +170,11 @@ struct PkMin {
     // stores: gfx9 counts loads and stores in one in-order vmcnt, so a load issued inside the k-mer loop waits for every copy-out
     // store queued before it.  A word is picked by its wave-uniform index (s_set_gpr_idx + v_mov); longer reads load the rest.
     u32x16 wr;
+    // The staged u16 of k_minimizer_pk: 2 * position + strand, built at hash time by ONE v_addc_co_u32 (the strand compare's mask as
+    // carry-in) and stored as it is; pk_copyout<.., true> turns it into strand << 31 | position with one v_alignbit.  RINGM keeps
+    // strand << 15 | position (flush_groups and flush_last read it), SELM stages nothing.
+    static constexpr bool POS2 = !RINGM && !SELM;
+    u32 i2;  // POS2: 2 * i0 of the block being hashed, in a VGPR
 
     __device__ __forceinline__ void set_words(const PkWords &p) {
         wr = (u32x16){p.a.x, p.a.y, p.a.z, p.a.w, p.b.x, p.b.y, p.b.z, p.b.w, p.c.x, p.c.y, p.c.z, p.c.w, p.d.x, p.d.y, p.d.z, p.d.w};
@@ -238,7 +252,12 @@ struct PkMin {
     __device__ __forceinline__ void emit_staged(u32 pbase) {
         const u32 b = (bm >> IDX) & 1u;  // v_bfe_u32
         u32 pv;  // strand << 15 | position: one v_add3_u32 (scalar base, inline slot number); as C it is an s_add per step and a v_or
-        asm("v_add3_u32 %0, %1, %2, %3" : "=v"(pv) : "v"(SB[O]), "s"(pbase), "n"(O));
+        if constexpr (POS2) {
+            (void)pbase;
+            pv = SB[O];  // (2 * position + strand, complete since the slot was hashed)
+        } else {
+            asm("v_add3_u32 %0, %1, %2, %3" : "=v"(pv) : "v"(SB[O]), "s"(pbase), "n"(O));
+        }
 #if defined(PK_MASKST)  // dev: the staging writes under the selection bit's lane mask (about a sixth of the lanes), no branch
         {
             const u32 a0 = (u32)(uintptr_t)(lds + LY::SH) + slot, a1 = (u32)(uintptr_t)(lds + LY::SP) + (slot >> 2);
@@ -314,6 +333,10 @@ struct PkMin {
         fetch(0);
         if (XC < W) fetch(XC);
         const u32 pbase = (u32)__builtin_amdgcn_readfirstlane((int)(i0 - (u32)W));
+        if constexpr (POS2) {
+            i2 = 2u * i0;
+            asm volatile("" : "+v"(i2));  // (one v_mov per block into a VGPR: with the carry-in the v_addc reads its one SGPR already)
+        }
         if (!FIRST) guard();
         u32 vb = 0;
         if (RAG && !FIRST) {  // bit o: the window ending at slot o exists for this lane
@@ -328,11 +351,18 @@ struct PkMin {
                 fetch(o + XC);
             }
             roll(xs[o]);
-            const lmask rev = lt64(rl, rh_, fl, fh_);
             if (!FIRST) this->template emit<PB + o, o>(pbase);  // the previous block's slot o, before its registers are re-used
+            const lmask rev = lt64(rl, rh_, fl, fh_);
             const u32 hl = sel(rev, rl, fl), hh = sel(rev, rh_, fh_);
+            if constexpr (POS2) {
+                // 2 * (i0 + o) + strand in one v_addc_co_u32: 2o (inline constant) + 2 i0 (a VGPR) + the strand mask as carry-in.  (The VOP3
+                // form, carry-in from the compare's SGPR pair: a VOP2 reading VCC would need two wait states behind the compare.)
+                lmask co;
+                asm("v_addc_co_u32_e64 %0, %1, %2, %3, %4" : "=v"(SB[o]), "=s"(co) : "n"(2 * o), "v"(i2), "s"(rev));
+            } else {
+                asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(SB[o]) : "v"(c8000), "s"(rev));  // strand << 15 in one select (0x8000 kept in a VGPR: VOP3 takes no literal)
+            }
             H[o] = ((u64)hh << 32) | hl;
-            asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(SB[o]) : "v"(c8000), "s"(rev));  // strand << 15 in one select (0x8000 kept in a VGPR: VOP3 takes no literal)
             u32 pk;  // (hh & ~31) | idx: one v_and_or_b32 with the mask in an SGPR (VOP3 takes no literal on gfx9: the compiler's form is and + or)
             asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(pk) : "v"(hh), "s"(0xffffffe0u), "n"(CB + o));
             if (o == 0) {
@@ -479,7 +509,8 @@ struct PkMin {
 // dependent LDS round trips per trip of four rows, 5.5 trips per unit.  Here the head words are read ONCE (lane c keeps word c, a row
 // takes its word with v_readlane: no LDS), and a trip is U = 8 rows, so a unit is three trips of two round trips (table entries, then
 // the staged tuples).
-template <int U, class LY = PkLds>
+// POS2: the staged u16 is 2 * position + strand (PkMin::POS2), else strand << 15 | position.
+template <int U, class LY = PkLds, bool POS2 = false>
 __device__ __forceinline__ void pk_copyout(char *lds, int lane, u32 cnt, u32 excl, u32 T, u64 base, const KArgs &a) {
     constexpr int NH = LY::NHEADS;
     u64 *s_heads = reinterpret_cast<u64 *>(lds + LY::HEADS);
@@ -534,7 +565,8 @@ __device__ __forceinline__ void pk_copyout(char *lds, int lane, u32 cnt, u32 exc
             const int off = __mul24((int)t, (int)(u32)(ent[j] >> 32)) + (int)(u32)ent[j];  // v_mad_i32_i24
             const u32 so = (!CHECK || t < T) ? (u32)off : 0u;
             hv[j] = *reinterpret_cast<const u64 *>(sh + so);
-            pv[j] = (u32)(int)*reinterpret_cast<const short *>(sp + (so >> 2));  // sign-extending read: the strand bit lands in bit 31
+            if constexpr (POS2) pv[j] = *reinterpret_cast<const u16 *>(sp + (so >> 2));
+            else pv[j] = (u32)(int)*reinterpret_cast<const short *>(sp + (so >> 2));  // sign-extending read: the strand bit lands in bit 31
         }
         if constexpr (U == 8) {
             __builtin_amdgcn_sched_barrier(0);
@@ -555,7 +587,8 @@ __device__ __forceinline__ void pk_copyout(char *lds, int lane, u32 cnt, u32 exc
                 asm volatile("" ::"v"(hv[j]));
 #endif
 #ifndef PK_NOPOSST
-                __builtin_nontemporal_store(pv[j] & 0x80007fffu, &gp[t]);
+                // strand << 31 | position: 2 pos + strand rotated right by one, or the strand's sign extension masked
+                __builtin_nontemporal_store(POS2 ? __builtin_amdgcn_alignbit(pv[j], pv[j], 1) : pv[j] & 0x80007fffu, &gp[t]);
 #else
                 asm volatile("" ::"v"(pv[j]));
 #endif
@@ -604,19 +637,29 @@ __global__ __launch_bounds__(64, 2) void k_minimizer_pk(KArgs a) {  // two waves
     const u32 lseg = a.fixcap / a.list_grid;  // this workgroup's segment of the list of reads for the exact machine (list_append)
     u32 lcur = 0;
     const u32 tku = a.tk ? a.tk : PK_TICKET;
+    // The next ticket is requested at the start of the third-to-last unit of the current one and taken at that unit's wait, so its
+    // first unit's descriptor and words enter the one-unit-ahead pipeline like any other unit's: only a wave's first unit loads its
+    // own (have == false).  Tickets of one or two units take the next ticket when they end, as every ticket did before.
+    const bool ahead = tku >= 3u;
+    u32 tv = 0;       // lane 0: the returned ticket (in flight from the request to the wait)
+    u32 nt = ~0u;     // first unit of the next ticket, once taken (>= nunits: there is none)
     for (u32 unit = next_ticket(a.ticket, lane) * tku, uend = unit + tku; unit < a.nunits; ++unit, ({
              if (unit == uend) {
-                 unit = next_ticket(a.ticket, lane) * tku;
+                 unit = ahead ? nt : next_ticket(a.ticket, lane) * tku;
                  uend = unit + tku;
              }
          })) {
         const u64 r = (u64)unit * 64 + lane;
-        const bool nxt = unit + 1 != uend && unit + 1 < a.nunits;  // the next unit is this wave's too: its words and descriptor are on the way
+        // the unit after the next one (its descriptor is requested now): past the ticket's end, the next ticket's first or second unit
+        const u64 u2 = (!ahead || unit + 2u < uend) ? (u64)unit + 2u : (u64)nt + (unit + 2u - uend);
+        // the next unit is this wave's too: its words and descriptor are on the way
+        const bool nxt = unit + 1 != uend ? unit + 1 < a.nunits : ahead && nt < a.nunits;
+        const bool ask = ahead && unit + 3u == uend;
         // Every load below is unconditional (indices beyond the batch are clamped to its last read; what such a load returns is never
         // used): a value defined on one path only would reach its wait through a copy made BEFORE the wait, i.e. from registers whose
         // load the compiler does not know to be in flight.
         const u64 rmax = a.n - 1;
-        if (!have) {  // first unit of a ticket: nothing was requested ahead
+        if (!have) {  // a wave's first unit, or the first of a ticket of one or two units: nothing was requested ahead
             d_cur = pk_load_u64(a.desc + (r < rmax ? r : rmax));
             d_n1 = pk_load_u64(a.desc + (r + 64 < rmax ? r + 64 : rmax));
             pk_wait_loads(d_cur, d_n1);
@@ -624,9 +667,11 @@ __global__ __launch_bounds__(64, 2) void k_minimizer_pk(KArgs a) {  // two waves
             pk_wait_loads(pw_cur);
         }
         PkWords pw_n1 = pk_load_words(a.words + (d_n1 >> 24));
-        u64 d_n2 = pk_load_u64(a.desc + (r + 128 < rmax ? r + 128 : rmax));
+        const u64 r2 = u2 * 64 + lane;
+        u64 d_n2 = pk_load_u64(a.desc + (r2 < rmax ? r2 : rmax));
         // the read's input flags (batches packed from ASCII have them): a load after the copy-out would wait for its stores
         u32 rfl = pk_load_u8(a.rflags ? a.rflags + (r < rmax ? r : rmax) : reinterpret_cast<const u8 *>(a.desc));
+        if (ask) pk_ticket_async(a.ticket, tv);
         const u64 d = d_cur;
         const PkWords pw = pw_cur;
         const u64 off = d >> 24, L = desc_len(a, d);
@@ -652,7 +697,8 @@ __global__ __launch_bounds__(64, 2) void k_minimizer_pk(KArgs a) {  // two waves
             if (ok) cnt = (lane < 32 ? pm.slot - col8 : top - pm.slot) / RB;
             tmin_lane = pm.tmin;
         }
-        pk_wait_loads(pw_n1, d_n2, rfl);  // the next unit's words and descriptor, requested a whole hashing phase ago, are in
+        pk_wait_loads(pw_n1, d_n2, rfl, tv);  // the next unit's words and descriptor (and the next ticket), requested a whole hashing phase ago, are in
+        if (ask) nt = (u32)__builtin_amdgcn_readfirstlane((int)tv) * tku;
         d_cur = d_n1;
         pw_cur = pw_n1;
         d_n1 = d_n2;
@@ -682,7 +728,7 @@ __global__ __launch_bounds__(64, 2) void k_minimizer_pk(KArgs a) {  // two waves
 #ifndef PK_CU
 #define PK_CU 8
 #endif
-        if (T) pk_copyout<PK_CU>(lds, lane, cnt, excl, T, base, a);
+        if (T) pk_copyout<PK_CU, LY, PkMin<W, LONG>::POS2>(lds, lane, cnt, excl, T, base, a);
 #endif
         if (r < a.n) {
             if (!((redo >> lane) & 1)) a.refs[ro] = ((base + excl) << 24) | cnt;  // (listed reads: the list pass writes theirs)

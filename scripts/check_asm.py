@@ -4,7 +4,7 @@
 1. Every inline-asm block that contains an SALU instruction writing SCC (s_and/s_or/s_xor/s_add/s_sub/s_lshl/s_lshr/s_bcnt/s_cmp ...)
    names "scc" in its clobber list.  (Round 2: a tie chain without the clobber lost whole reads' tuples in 6 % of the fuzz cases --
    the compiler kept a loop condition in SCC across the block.)
-2. The loads k_minimizer_pk / k_syncmer_pk issue from inline asm are invisible to the compiler's s_waitcnt pass (on purpose, kernels_pk.hpp).  In the
+2. The loads (and returning atomics) k_minimizer_pk / k_syncmer_pk issue from inline asm are invisible to the compiler's s_waitcnt pass (on purpose, kernels_pk.hpp).  In the
    generated ISA, between such a load and the hand-written `s_waitcnt vmcnt(0)` that follows it in the text, no instruction may
    mention the load's destination registers: a copy or a use placed there would read registers whose data has not arrived.
    (A linear scan of the text: conservative, it knows nothing of the control flow.)
@@ -74,7 +74,8 @@ def check_hidden_loads(ws=("11",), unit="k_minimizer_pk", macro="BSK_PK_WS", ext
                 continue
             code = s.split(";")[0]
             if in_asm:
-                if code.startswith("global_load") and not code.startswith("global_load_lds"):  # (LDS-DMA has no VGPR destination)
+                # (LDS-DMA has no VGPR destination; a returning atomic -- sc0 -- is a load of its first operand)
+                if (code.startswith("global_load") and not code.startswith("global_load_lds")) or (code.startswith("global_atomic") and " sc0" in code):
                     dst = code.split()[1].rstrip(",")
                     for r in regs(dst):
                         pending[r] = n
