@@ -30,7 +30,22 @@ const (
 	SinkCounts Sink = C.BSK_SINK_COUNTS // counts + the device-side digest only
 	SinkTuples Sink = C.BSK_SINK_TUPLES // every (hash, position, strand) tuple, in Next() order
 	SinkSets   Sink = C.BSK_SINK_SETS   // per record: ascending distinct hashes with hash <= MaxUint64/scale (iterator.go:181-185)
+	SinkHits   Sink = C.BSK_SINK_HITS   // per record: the targets of an index that share values with its set (OpenFilesSearch / OpenMemorySearch)
 )
+
+// PipelineSearch mirrors bsk_pipeline_search: what a SinkHits pipeline searches every chunk's sets for.  Index may belong to any
+// engine and device (the pipeline attaches a handle per worker) and must outlive the pipeline; it must have been built from sets of
+// the same parameters and scale as the run's.
+type PipelineSearch struct {
+	Index  *Index
+	Params SearchParams
+	TopN   uint32 // 0: every hit, targets ascending; n: every record's n best, largest shared count first
+}
+
+func (ps *PipelineSearch) c() C.bsk_pipeline_search {
+	return C.bsk_pipeline_search{index: ps.Index.h, params: C.bsk_search_params{min_shared: C.uint32_t(ps.Params.MinShared),
+		min_query_cov: C.double(ps.Params.MinQueryCov), min_target_cov: C.double(ps.Params.MinTargetCov)}, top_n: C.uint32_t(ps.TopN)}
+}
 
 // PipelineConfig mirrors bsk_pipeline_config.
 type PipelineConfig struct {
@@ -59,12 +74,15 @@ type Chunk struct {
 	Status      []uint8
 	Hash        []uint64
 	Pos         []uint32 // SinkTuples, kinds with positions: bit 31 = strand (BSK_POS_STRAND_BIT); nil otherwise
+	Target      []uint32 // SinkHits: record i owns Target / Shared[Offsets[i]:Offsets[i+1]]; nil otherwise
+	Shared      []uint32
 }
 
 // Pipeline is a running bsk_pipeline.
 type Pipeline struct {
 	h     *C.bsk_pipeline
 	devs  *C.int
+	index *Index // SinkHits: the searched index, kept alive until Close
 	held  *C.bsk_chunk
 	Stats PipelineStats // filled by Close
 
@@ -126,6 +144,43 @@ func OpenMemory(cfg PipelineConfig, bytes unsafe.Pointer, offsets unsafe.Pointer
 	return pl, nil
 }
 
+// OpenFilesSearch is OpenFiles with cfg.Sink == SinkHits: bsk_pipeline_open_fastx_search.
+func OpenFilesSearch(cfg PipelineConfig, paths []string, p C.bsk_params, search PipelineSearch) (*Pipeline, error) {
+	if len(paths) == 0 || len(cfg.Devices) == 0 || search.Index == nil {
+		return nil, errors.New("biosketch: OpenFilesSearch needs paths, devices and an index")
+	}
+	cc, devs := cfg.c()
+	cs := make([]*C.char, len(paths))
+	for i, s := range paths {
+		cs[i] = C.CString(s)
+		defer C.free(unsafe.Pointer(cs[i]))
+	}
+	sc := search.c()
+	pl := &Pipeline{devs: devs, done: make(chan struct{}), index: search.Index}
+	rc := C.bsk_pipeline_open_fastx_search(&cc, (**C.char)(unsafe.Pointer(&cs[0])), C.int(len(paths)), &p, &sc, &pl.h)
+	if rc != C.BSK_OK {
+		C.free(unsafe.Pointer(devs))
+		return nil, fmt.Errorf("bsk_pipeline_open_fastx_search: %s", C.GoString(C.bsk_err_name(rc)))
+	}
+	return pl, nil
+}
+
+// OpenMemorySearch is OpenMemory with cfg.Sink == SinkHits: bsk_pipeline_open_memory_search.
+func OpenMemorySearch(cfg PipelineConfig, bytes unsafe.Pointer, offsets unsafe.Pointer, n uint64, repeat int, p C.bsk_params, search PipelineSearch) (*Pipeline, error) {
+	if len(cfg.Devices) == 0 || search.Index == nil {
+		return nil, errors.New("biosketch: OpenMemorySearch needs devices and an index")
+	}
+	cc, devs := cfg.c()
+	sc := search.c()
+	pl := &Pipeline{devs: devs, done: make(chan struct{}), index: search.Index}
+	rc := C.bsk_pipeline_open_memory_search(&cc, (*C.uint8_t)(bytes), (*C.uint64_t)(offsets), C.uint64_t(n), C.int(repeat), &p, &sc, &pl.h)
+	if rc != C.BSK_OK {
+		C.free(unsafe.Pointer(devs))
+		return nil, fmt.Errorf("bsk_pipeline_open_memory_search: %s", C.GoString(C.bsk_err_name(rc)))
+	}
+	return pl, nil
+}
+
 // Next returns the next chunk in input order, nil at the end (bsk_pipeline_next); the chunk returned before is released.
 func (pl *Pipeline) Next() (*Chunk, error) {
 	if pl.held != nil {
@@ -178,6 +233,13 @@ func (pl *Pipeline) fetch() (out *Chunk, raw *C.bsk_chunk, err error) {
 		}
 	} else if c.pos32 != nil && nv > 0 {
 		out.Pos = (*[1 << 38]uint32)(unsafe.Pointer(c.pos32))[:nv:nv]
+	}
+	if c.sink == C.BSK_SINK_HITS && nv > 0 {
+		var tp, sp *C.uint32_t
+		if C.bsk_chunk_hits(c, &tp, &sp) == C.BSK_OK {
+			out.Target = (*[1 << 38]uint32)(unsafe.Pointer(tp))[:nv:nv]
+			out.Shared = (*[1 << 38]uint32)(unsafe.Pointer(sp))[:nv:nv]
+		}
 	}
 	return out, c, nil
 }
@@ -251,6 +313,8 @@ func (pl *Pipeline) Close() error {
 	var st C.bsk_pipeline_stats
 	rc := C.bsk_pipeline_close(pl.h, &st)
 	pl.h = nil
+	runtime.KeepAlive(pl.index) // the pipeline's handles were attached to it until here
+	pl.index = nil
 	C.free(unsafe.Pointer(pl.devs))
 	pl.Stats = statsFromC(&st)
 	if rc != C.BSK_OK && rc != -1 { // -1: closed before the end of the input

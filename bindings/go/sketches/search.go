@@ -142,3 +142,29 @@ func (h *Hits) DevicePointers() (offsets, target, shared unsafe.Pointer) {
 	runtime.KeepAlive(h)
 	return unsafe.Pointer(o), unsafe.Pointer(t), unsafe.Pointer(s)
 }
+
+// Attach returns a handle on the index for another engine (bsk_index_attach): on the same device the device arrays are shared
+// (reference counted), on another device they are copied there once.  The handle is searched like any Index; the handles of an
+// index may be released in any order, but not while a search on that same handle runs.
+func (ix *Index) Attach(e *Engine) (*Index, error) {
+	h := &Index{eng: e}
+	rc := C.bsk_index_attach(e.ctx, ix.h, &h.h)
+	runtime.KeepAlive(ix)
+	if err := e.err(rc); err != nil {
+		return nil, err
+	}
+	runtime.SetFinalizer(h, func(h *Index) { C.bsk_index_release(h.h) })
+	return h, nil
+}
+
+// Top keeps every query's min(n, hits) best hits: largest shared count first, ties by ascending target id (bsk_hits_top).
+// into: nil, or the Hits of an earlier Top on this engine, whose device arrays are kept and only grow.
+func (h *Hits) Top(n uint32, into *Hits) (*Hits, error) {
+	if into == nil {
+		into = &Hits{eng: h.eng}
+		runtime.SetFinalizer(into, func(t *Hits) { C.bsk_hits_release(t.h) })
+	}
+	rc := C.bsk_hits_top(h.eng.ctx, h.h, C.uint32_t(n), &into.h)
+	runtime.KeepAlive(h)
+	return into, h.eng.err(rc)
+}

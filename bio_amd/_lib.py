@@ -55,7 +55,7 @@ class Chunk(C.Structure):
                 ("pos16", C.c_void_p), ("pos32", C.c_void_p), ("opaque", C.c_void_p)]
 
 
-SINK_COUNTS, SINK_TUPLES, SINK_SETS = 0, 1, 2
+SINK_COUNTS, SINK_TUPLES, SINK_SETS, SINK_HITS = 0, 1, 2, 3
 CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(Chunk))
 
 
@@ -67,6 +67,11 @@ class Params(C.Structure):
 class SearchParams(C.Structure):
     """bsk_search_params (include/biosketch.h)"""
     _fields_ = [("min_shared", C.c_uint32), ("reserved", C.c_uint32), ("min_query_cov", C.c_double), ("min_target_cov", C.c_double)]
+
+
+class PipelineSearch(C.Structure):
+    """bsk_pipeline_search (include/biosketch.h): what a BSK_SINK_HITS pipeline searches every chunk's sets for"""
+    _fields_ = [("index", C.c_void_p), ("params", SearchParams), ("top_n", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 # every symbol include/biosketch.h declares: (name, restype, argtypes)
@@ -157,6 +162,11 @@ SYMBOLS = [
     ("bsk_hits_fetch", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.c_uint64]),
     ("bsk_hits_device", C.c_int, [_vp, _pp, _pp, _pp]),
     ("bsk_hits_release", None, [_vp]),
+    ("bsk_index_attach", C.c_int, [_vp, _vp, _pp]),
+    ("bsk_hits_top", C.c_int, [_vp, _vp, C.c_uint32, _pp]),
+    ("bsk_pipeline_open_fastx_search", C.c_int, [C.POINTER(PipelineConfig), C.POINTER(C.c_char_p), C.c_int, C.POINTER(Params), C.POINTER(PipelineSearch), _pp]),
+    ("bsk_pipeline_open_memory_search", C.c_int, [C.POINTER(PipelineConfig), _vp, _vp, C.c_uint64, C.c_int, C.POINTER(Params), C.POINTER(PipelineSearch), _pp]),
+    ("bsk_chunk_hits", C.c_int, [C.POINTER(Chunk), _pp, _pp]),
 ]
 SETS_PER_SEQUENCE, SETS_WHOLE_BATCH = 0, 1
 

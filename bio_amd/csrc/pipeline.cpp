@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "host_types.hpp"
+#include "search_internal.hpp"
 
 namespace {
 std::mutex g_h2d_mutex[16], g_d2h_mutex[16];  // per device: one copy per direction at a time (run_pipeline)
@@ -508,6 +509,12 @@ struct bsk_pipeline {
     // the block-parallel reader's figures, filled in when its file closes
     int reader_threads = 0;
     uint64_t reparsed = 0;
+    // BSK_SINK_HITS: the caller's index and what to search for; every worker searches a handle of its own.  The first worker of a device
+    // attaches to the caller's index (a copy when that lives on another device), the others of the device to that worker's handle (shared)
+    bsk_pipeline_search search{};
+    std::mutex ixm;
+    std::map<int, bsk_index *> dev_root;
+    std::vector<bsk_index *> handles;  // [worker], released once every worker has left (a device's first handle is what its later workers attach to)
 
     void fail(int code, const std::string &text) {
         int z = 0;
@@ -528,6 +535,7 @@ struct bsk_pipeline {
     }
     void producer_main();
     void worker_main(int w);
+    int attach_index(int w, int device, bsk_ctx *ctx, const bsk_index **out);
     int start();
     void join_all();
 };
@@ -619,11 +627,15 @@ void bsk_pipeline::worker_main(int w) {
     bsk_batch *batch = nullptr;
     bsk_result *res = nullptr;
     bsk_sets *sets = nullptr;
+    bsk_hits *hits = nullptr, *top = nullptr;
+    const bsk_index *my_ix = nullptr;
     bsk_pipeline_stats loc;
     memset(&loc, 0, sizeof loc);
     const bsk_params *p = &params;
     if (bsk_ctx_create(device, &ctx) != BSK_OK) {
         fail(BSK_ERR_NO_DEVICE, "bsk_ctx_create");
+    } else if (sink == BSK_SINK_HITS && attach_index(w, device, ctx, &my_ix) != BSK_OK) {
+        fail(BSK_ERR_DEVICE, std::string("bsk_index_attach: ") + bsk_last_error(ctx));
     } else {
         for (;;) {
             OutBuf *ob = free_out.pop();
@@ -728,6 +740,35 @@ void bsk_pipeline::worker_main(int w) {
                     for (uint64_t j = 0; j < nv; ++j) sum += pub.hash[j];
                     pub.checksum = sum;
                 }
+            } else if (rc == BSK_OK && sink == BSK_SINK_HITS) {
+                // the sets stay on the device: searched there, reduced there to the best top_n per read, and only the hits cross the link
+                rc = bsk_result_sets_reuse(ctx, res, BSK_SETS_PER_SEQUENCE, sets_scale, &sets);
+                if (rc == BSK_OK) rc = bsk_index_search(ctx, my_ix, sets, &search.params, &hits);
+                if (rc == BSK_OK && search.top_n) rc = bsk_hits_top(ctx, hits, search.top_n, &top);
+                const bsk_hits *out = search.top_n ? top : hits;
+                uint64_t nqh = 0, nh = 0;
+                if (rc == BSK_OK) rc = bsk_hits_info(out, &nqh, &nh);
+                const bool narrow = nh < (1ull << 32);
+                if (rc == BSK_OK && (!ob->off.ensure((nqh + 1) * (narrow ? 4 : 8)) || !ob->st.ensure(nr + 1) || !ob->hash.ensure((nh + 1) * 4) || !ob->pos.ensure((nh + 1) * 4)))
+                    rc = BSK_ERR_NOMEM;
+                if (rc == BSK_OK) {
+                    std::unique_lock<std::mutex> lk(g_d2h_mutex[device & 15], std::defer_lock);
+                    if (g_copy_locks) lk.lock();
+                    if (narrow) rc = hits_fetch_narrow(ctx, out, (uint32_t *)ob->off.p, (uint32_t *)ob->hash.p, (uint32_t *)ob->pos.p, nh + 1);
+                    else rc = bsk_hits_fetch(ctx, out, 0, nqh, (uint64_t *)ob->off.p, (uint32_t *)ob->hash.p, (uint32_t *)ob->pos.p, nh + 1);
+                    if (rc == BSK_OK) rc = bsk_result_fetch_status(ctx, res, 0, nr, (uint8_t *)ob->st.p);
+                }
+                if (narrow) pub.offsets32 = (const uint32_t *)ob->off.p;
+                else pub.offsets64 = (const uint64_t *)ob->off.p;
+                pub.status = (const uint8_t *)ob->st.p;
+                pub.n_values = nh;  // (target[] and shared[]: bsk_chunk_hits)
+                pub.link_bytes = nr * (narrow ? 5 : 9) + nh * 8;
+                if (rc == BSK_OK && host_checksum) {
+                    const uint32_t *t = (const uint32_t *)ob->hash.p, *sh = (const uint32_t *)ob->pos.p;
+                    uint64_t sum = 0;
+                    for (uint64_t j = 0; j < nh; ++j) sum += (uint64_t)t[j] + sh[j];
+                    pub.checksum = sum;
+                }
             } else if (rc == BSK_OK) {  // BSK_SINK_COUNTS: nothing but counts and the device-side digest leave the device
                 uint64_t ck = 0, ntt = 0;
                 rc = bsk_result_digest(ctx, res, &ck, &ntt, nullptr);
@@ -752,6 +793,8 @@ void bsk_pipeline::worker_main(int w) {
         }
     }
     if (sets) bsk_sets_release(sets);
+    bsk_hits_release(hits);
+    bsk_hits_release(top);
     bsk_result_release(res);
     bsk_batch_destroy(batch);
     if (ctx) bsk_ctx_destroy(ctx);
@@ -773,6 +816,18 @@ void bsk_pipeline::worker_main(int w) {
     ocv.notify_all();
 }
 
+int bsk_pipeline::attach_index(int w, int device, bsk_ctx *ctx, const bsk_index **out) {
+    std::lock_guard<std::mutex> l(ixm);
+    auto it = dev_root.find(device);
+    bsk_index *h = nullptr;
+    const int rc = bsk_index_attach(ctx, it == dev_root.end() ? search.index : it->second, &h);
+    if (rc != BSK_OK) return rc;
+    if (it == dev_root.end()) dev_root[device] = h;
+    handles[(size_t)w] = h;
+    *out = h;
+    return BSK_OK;
+}
+
 int bsk_pipeline::start() {
     const int n_dev = (int)devices.size();
     for (int d = 0; d < n_dev; ++d)
@@ -791,6 +846,7 @@ int bsk_pipeline::start() {
     pin0 = g_pin_ns.load();
     producers_left = n_producers;
     workers_alive = n_workers;
+    handles.assign((size_t)n_workers, nullptr);
     for (int pi = 0; pi < n_producers; ++pi) producers.emplace_back([this] { producer_main(); });
     for (int w = 0; w < n_workers; ++w) workers.emplace_back([this, w] { worker_main(w); });
     return BSK_OK;
@@ -801,6 +857,9 @@ void bsk_pipeline::join_all() {
     joined = true;
     for (auto &t : producers) t.join();
     for (auto &t : workers) t.join();
+    for (auto *h : handles) bsk_index_release(h);  // (a handle is plain memory and a reference: its worker's context may be gone)
+    handles.clear();
+    dev_root.clear();
     for (auto &c : chunks)
         if (c.slot && !c.slot->closed.load()) c.slot->src->discard(&c);
     for (int i = 0; i < set->count(); ++i)
@@ -990,10 +1049,20 @@ struct FileSet : SourceSet {
 };
 }  // namespace
 
-extern "C" int bsk_pipeline_open_fastx(const bsk_pipeline_config *cfg, const char *const *paths, int n_paths, const bsk_params *p, bsk_pipeline **out) {
+// the hits sink's arguments: check_config's rules with sink == BSK_SINK_HITS, and the search's own
+static int check_search_config(const bsk_pipeline_config *cfg, const bsk_params *p, const bsk_pipeline_search *s) {
+    if (!cfg || !p || !s || !cfg->devices || cfg->n_devices < 1 || cfg->n_devices > 64 || cfg->n_streams < 1 || cfg->n_streams > 16) return BSK_ERR_ARG;
+    if (cfg->sink != BSK_SINK_HITS || cfg->sets_scale < 0) return BSK_ERR_ARG;
+    if (!s->index || s->reserved != 0 || s->params.reserved != 0) return BSK_ERR_ARG;
+    if (!(s->params.min_query_cov >= 0.0 && s->params.min_query_cov <= 1.0) || !(s->params.min_target_cov >= 0.0 && s->params.min_target_cov <= 1.0)) return BSK_ERR_ARG;
+    return BSK_OK;
+}
+
+static int open_fastx(const bsk_pipeline_config *cfg, const char *const *paths, int n_paths, const bsk_params *p, const bsk_pipeline_search *s, bool with_search,
+                      bsk_pipeline **out) {
     if (!out) return BSK_ERR_ARG;
     *out = nullptr;
-    int rc = check_config(cfg, p);
+    int rc = with_search ? check_search_config(cfg, p, s) : check_config(cfg, p);
     if (rc != BSK_OK || !paths || n_paths < 1 || cfg->n_readers < 0) return BSK_ERR_ARG;
     auto *set = new FileSet();
     for (int i = 0; i < n_paths; ++i) {
@@ -1011,17 +1080,25 @@ extern "C" int bsk_pipeline_open_fastx(const bsk_pipeline_config *cfg, const cha
     const int budget = tv && atoi(tv) > 0 ? atoi(tv) : std::max(1, (int)std::thread::hardware_concurrency() - n_workers - n_readers);
     set->threads_per_file = std::max(1, std::min(budget, 12) / n_readers);
     bsk_pipeline *pl = new_pipeline(cfg, p);
+    if (with_search) pl->search = *s;
     set->owner = pl;
     pl->set.reset(set);
     pl->n_producers = n_readers;
     return start_or_drop(pl, out);
 }
+extern "C" int bsk_pipeline_open_fastx(const bsk_pipeline_config *cfg, const char *const *paths, int n_paths, const bsk_params *p, bsk_pipeline **out) {
+    return open_fastx(cfg, paths, n_paths, p, nullptr, false, out);
+}
+extern "C" int bsk_pipeline_open_fastx_search(const bsk_pipeline_config *cfg, const char *const *paths, int n_paths, const bsk_params *p,
+                                              const bsk_pipeline_search *s, bsk_pipeline **out) {
+    return open_fastx(cfg, paths, n_paths, p, s, true, out);
+}
 
-extern "C" int bsk_pipeline_open_memory(const bsk_pipeline_config *cfg, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, int repeat,
-                                        const bsk_params *p, bsk_pipeline **out) {
+static int open_memory(const bsk_pipeline_config *cfg, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, int repeat, const bsk_params *p,
+                       const bsk_pipeline_search *s, bool with_search, bsk_pipeline **out) {
     if (!out) return BSK_ERR_ARG;
     *out = nullptr;
-    if (check_config(cfg, p) != BSK_OK || !bytes || !offsets || !n || repeat < 1) return BSK_ERR_ARG;
+    if ((with_search ? check_search_config(cfg, p, s) : check_config(cfg, p)) != BSK_OK || !bytes || !offsets || !n || repeat < 1) return BSK_ERR_ARG;
     auto *src = new MemorySource();
     src->bytes = bytes;
     src->offsets = offsets;
@@ -1029,10 +1106,29 @@ extern "C" int bsk_pipeline_open_memory(const bsk_pipeline_config *cfg, const ui
     src->repeat = repeat;
     src->alphabet = cfg->alphabet < 0 ? BSK_ALPHA_DNA : cfg->alphabet;
     bsk_pipeline *pl = new_pipeline(cfg, p);
+    if (with_search) pl->search = *s;
     pl->own_src.reset(src);
     pl->set.reset(new OneSource(src));
     pl->n_producers = 1;
     return start_or_drop(pl, out);
+}
+extern "C" int bsk_pipeline_open_memory(const bsk_pipeline_config *cfg, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, int repeat,
+                                        const bsk_params *p, bsk_pipeline **out) {
+    return open_memory(cfg, bytes, offsets, n, repeat, p, nullptr, false, out);
+}
+extern "C" int bsk_pipeline_open_memory_search(const bsk_pipeline_config *cfg, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, int repeat,
+                                               const bsk_params *p, const bsk_pipeline_search *s, bsk_pipeline **out) {
+    return open_memory(cfg, bytes, offsets, n, repeat, p, s, true, out);
+}
+
+extern "C" int bsk_chunk_hits(const bsk_chunk *c, const uint32_t **target, const uint32_t **shared) {
+    if (target) *target = nullptr;
+    if (shared) *shared = nullptr;
+    if (!c || !c->opaque || c->sink != BSK_SINK_HITS) return BSK_ERR_ARG;
+    const OutBuf *ob = static_cast<const OutBuf *>(c->opaque);
+    if (target) *target = (const uint32_t *)ob->hash.p;
+    if (shared) *shared = (const uint32_t *)ob->pos.p;
+    return BSK_OK;
 }
 
 // ---- the statistics-only entry points (rounds 2-4): one consumer loop over the pipeline object, the digest folded by the workers ----

@@ -22,6 +22,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -30,17 +31,25 @@
 
 #include "biosketch.h"
 #include "host_types.hpp"
+#include "search_internal.hpp"
 #include "sets_internal.hpp"
 
-struct bsk_index {
-    bsk_ctx *ctx = nullptr;
-    u64 n_targets = 0, n_postings = 0, n_distinct = 0, max_bucket = 0, device_bytes = 0;
-    int bits = 0;              // directory over the top `bits` bits of the mixed key
+// The device arrays of an index, on one device: read-only once built, shared by every handle of that device (bsk_index_attach) and
+// freed when the last of them is released.
+struct IndexArrays {
+    std::atomic<int> refs{1};
+    int device = 0;
     u64 *keys = nullptr;       // [U] distinct mixed keys, ascending
     u32 *post_off = nullptr;   // [U + 1] postings of key u: post_tgt[post_off[u] .. post_off[u + 1])
     u32 *post_tgt = nullptr;   // [P] target ids, ascending inside a key
     u32 *dir = nullptr;        // [2^bits + 1] first key of every bucket
     u32 *tsize = nullptr;      // [n_targets] |t|
+};
+struct bsk_index {
+    bsk_ctx *ctx = nullptr;    // the context this handle is searched on (never dereferenced by a release: it may be gone by then)
+    u64 n_targets = 0, n_postings = 0, n_distinct = 0, max_bucket = 0, device_bytes = 0;
+    int bits = 0;              // directory over the top `bits` bits of the mixed key
+    IndexArrays *a = nullptr;
 };
 
 struct bsk_hits {
@@ -328,6 +337,203 @@ __global__ __launch_bounds__(256) void k_sr_move(const u64 *stage_off, const u64
     }
 }
 
+// ---- the n best hits of every query (bsk_hits_top) ----
+// A hit's rank is the key (shared << 32) | ~target: larger is better, and the keys of one query are distinct (its targets are).
+#define TOP_GROUP 16       // hits a group of 16 lanes ranks in registers, one per lane
+#define TOP_SELECT_N 16    // the largest n taken by n rounds of a wave-wide maximum (any number of hits)
+#define TOP_LDS_KEYS 1024  // keys one wavefront sorts in LDS: 8 KB, the budget of k_sr_small (SR_CAP u32 there, u64 keys here)
+#define TOP_WAVES 4        // wavefronts per workgroup of k_top_select / k_top_lds
+__device__ __forceinline__ u64 top_key(u32 s, u32 t) { return ((u64)s << 32) | (u32)~t; }
+__device__ __forceinline__ u64 wave_max_u64(u64 v) {
+    for (int d = 32; d; d >>= 1) {
+        const u64 t = __shfl_xor(v, d, 64);
+        v = t > v ? t : v;
+    }
+    return v;
+}
+struct TopCnt {  // what a query keeps: min(n, its hits)
+    const u64 *off;
+    u64 n;
+    __device__ __forceinline__ u64 operator()(u64 q) const {
+        const u64 c = off[q + 1] - off[q];
+        return c < n ? c : n;
+    }
+};
+struct TopLargeOf {  // queries beyond one wavefront's LDS: their count (count_only) or their hits
+    const u64 *off;
+    bool count_only;
+    __device__ __forceinline__ u64 operator()(u64 q) const {
+        const u64 c = off[q + 1] - off[q];
+        return c > TOP_LDS_KEYS ? (count_only ? 1 : c) : 0;
+    }
+};
+// cnt[0] = queries of 1 .. TOP_GROUP hits, cnt[1] = queries of TOP_GROUP + 1 .. wave_hi hits
+__global__ __launch_bounds__(256) void k_top_classes(const u64 *off, u64 nq, u64 wave_hi, u64 *cnt) {
+    u32 g = 0, w = 0;
+    for (u64 q = (u64)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (u64)gridDim.x * blockDim.x) {
+        const u64 c = off[q + 1] - off[q];
+        g += c >= 1 && c <= TOP_GROUP;
+        w += c > TOP_GROUP && c <= wave_hi;
+    }
+    for (int d = 32; d; d >>= 1) {
+        g += __shfl_xor(g, d, 64);
+        w += __shfl_xor(w, d, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (g) atomicAdd((unsigned long long *)cnt, (unsigned long long)g);
+        if (w) atomicAdd((unsigned long long *)cnt + 1, (unsigned long long)w);
+    }
+}
+__global__ __launch_bounds__(256) void k_top_maxshared(const u32 *sh, u64 n, u64 *mx) {
+    u32 m = 0;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) m = sh[i] > m ? sh[i] : m;
+    m = wave_max_u32(m);
+    if ((threadIdx.x & 63) == 0 && m) atomicMax((unsigned long long *)mx, (unsigned long long)m);
+}
+// queries of at most TOP_GROUP hits, a group of 16 lanes each: a lane's hit goes to the place (number of better keys of the group)
+__global__ __launch_bounds__(256) void k_top_group(const u64 *off, const u32 *tgt, const u32 *sh, u64 nq, u32 n, const u64 *toff, u32 *otgt, u32 *osh) {
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((u64)gridDim.x * blockDim.x) >> 6;
+    const u32 l = threadIdx.x & 15, g = (threadIdx.x & 63) >> 4;
+    for (u64 q0 = wave * 4; q0 < nq; q0 += nw * 4) {  // (the whole wavefront stays in step: the shuffles read every lane)
+        const u64 q = q0 + g;
+        u64 a = 0, c = 0;
+        if (q < nq) {
+            a = off[q];
+            c = off[q + 1] - a;
+        }
+        const bool mine = c <= TOP_GROUP && l < c;
+        u32 t = 0, s = 0;
+        if (mine) {
+            t = tgt[a + l];
+            s = sh[a + l];
+        }
+        const u64 key = mine ? top_key(s, t) : 0;  // (a listed pair shares a value: its key is not 0)
+        u32 rank = 0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) rank += __shfl(key, j, 16) > key;
+        if (mine && rank < n) {
+            const u64 o = toff[q] + rank;
+            otgt[o] = t;
+            osh[o] = s;
+        }
+    }
+}
+// queries of more than TOP_GROUP hits and n <= TOP_SELECT_N: round r takes the largest key below round r - 1's.  A wavefront looks at
+// qb (a power of two <= 64) consecutive queries at a time, one per lane, and then serves those that are its kind one after the other.
+__global__ __launch_bounds__(64 * TOP_WAVES) void k_top_select(const u64 *off, const u32 *tgt, const u32 *sh, u64 nq, u32 n, u32 qb, const u64 *toff, u32 *otgt,
+                                                               u32 *osh) {
+    const u32 lane = threadIdx.x & 63;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((u64)gridDim.x * blockDim.x) >> 6;
+    for (u64 q0 = wave * qb; q0 < nq; q0 += nw * qb) {
+        const u64 ql = q0 + lane;
+        const u64 cl = lane < qb && ql < nq ? off[ql + 1] - off[ql] : 0;
+        u64 todo = __ballot(cl > TOP_GROUP);
+        while (todo) {
+            const u64 q = q0 + (u64)__builtin_ctzll(todo);
+            todo &= todo - 1;
+            const u64 a = off[q], c = off[q + 1] - a, o = toff[q];
+            const u32 keep = c < n ? (u32)c : n;
+            const bool one = c <= 64;  // a key per lane: read once
+            const u64 held = one && lane < c ? top_key(sh[a + lane], tgt[a + lane]) : 0;
+            u64 prev = 0;
+            for (u32 r = 0; r < keep; ++r) {
+                u64 best = 0;
+                if (one) {
+                    best = (r == 0 || held < prev) ? held : 0;
+                } else {
+                    for (u64 i = lane; i < c; i += 64) {
+                        const u64 k = top_key(sh[a + i], tgt[a + i]);
+                        if ((r == 0 || k < prev) && k > best) best = k;
+                    }
+                }
+                best = wave_max_u64(best);
+                prev = best;
+                if (lane == 0) {
+                    otgt[o + r] = ~(u32)best;
+                    osh[o + r] = (u32)(best >> 32);
+                }
+            }
+        }
+    }
+}
+// queries of TOP_GROUP + 1 .. TOP_LDS_KEYS hits and n > TOP_SELECT_N: the inverted keys (~shared << 32) | target sorted ascending in
+// LDS (bitonic, as k_sr_small sorts its target ids), the first min(n, hits) written out
+__global__ __launch_bounds__(64 * TOP_WAVES) void k_top_lds(const u64 *off, const u32 *tgt, const u32 *sh, u64 nq, u32 n, u32 qb, const u64 *toff, u32 *otgt,
+                                                            u32 *osh) {
+    __shared__ u64 lds[TOP_WAVES][TOP_LDS_KEYS];
+    u64 *buf = lds[threadIdx.x >> 6];
+    const u32 lane = threadIdx.x & 63;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((u64)gridDim.x * blockDim.x) >> 6;
+    for (u64 q0 = wave * qb; q0 < nq; q0 += nw * qb) {
+        const u64 ql = q0 + lane;
+        const u64 cl = lane < qb && ql < nq ? off[ql + 1] - off[ql] : 0;
+        u64 todo = __ballot(cl > TOP_GROUP && cl <= TOP_LDS_KEYS);
+        while (todo) {
+            const u64 q = q0 + (u64)__builtin_ctzll(todo);
+            todo &= todo - 1;
+            const u64 a = off[q], o = toff[q];
+            const u32 c = (u32)(off[q + 1] - a);  // TOP_GROUP < c <= TOP_LDS_KEYS
+            const u32 keep = c < n ? c : n;
+            const u32 c2 = 1u << (32 - __builtin_clz(c - 1));  // <= TOP_LDS_KEYS (a power of two)
+            for (u32 i = lane; i < c2; i += 64) buf[i] = i < c ? ~top_key(sh[a + i], tgt[a + i]) : ~0ULL;  // (no inverted key is ~0: shared >= 1)
+            wave_sync_lds();
+            for (u32 k = 2; k <= c2; k <<= 1) {
+                for (u32 j = k >> 1; j > 0; j >>= 1) {
+                    for (u32 i = lane; i < c2; i += 64) {
+                        const u32 p = i ^ j;
+                        if (p > i) {
+                            const u64 x = buf[i], y = buf[p];
+                            if ((x > y) == ((i & k) == 0)) {
+                                buf[i] = y;
+                                buf[p] = x;
+                            }
+                        }
+                    }
+                    wave_sync_lds();
+                }
+            }
+            for (u32 i = lane; i < keep; i += 64) {
+                const u64 k = buf[i];
+                otgt[o + i] = (u32)k;
+                osh[o + i] = ~(u32)(k >> 32);
+            }
+            wave_sync_lds();  // every lane is done with the buffer before the next query fills it
+        }
+    }
+}
+// queries of more than TOP_LDS_KEYS hits and n > TOP_SELECT_N: slot s = the s-th of them; hit p of the query (its targets ascend with
+// p) gets the key (slot << (bs + bp)) | ((max_shared - shared) << bp) | p, so one ascending sort of all keys leaves every slot's hits
+// where the emit put them, best first
+__global__ __launch_bounds__(256) void k_top_list(const u64 *off, u64 nq, const u64 *lslot, u32 *lq) {
+    for (u64 q = (u64)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (u64)gridDim.x * blockDim.x)
+        if (off[q + 1] - off[q] > TOP_LDS_KEYS) lq[lslot[q]] = (u32)q;
+}
+__global__ __launch_bounds__(256) void k_top_emit(const u64 *off, const u32 *sh, const u32 *lq, u64 nl, const u64 *loff, u64 max_shared, u32 bs, u32 bp, u64 *lkeys) {
+    const u32 lane = threadIdx.x & 63;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((u64)gridDim.x * blockDim.x) >> 6;
+    for (u64 slot = wave; slot < nl; slot += nw) {
+        const u32 q = lq[slot];
+        const u64 a = off[q], c = off[q + 1] - a, d = loff[q], hi = slot << (bs + bp);
+        for (u64 p = lane; p < c; p += 64) lkeys[d + p] = hi | ((max_shared - sh[a + p]) << bp) | p;
+    }
+}
+__global__ __launch_bounds__(256) void k_top_place(const u64 *lkeys, u64 L, const u64 *off, const u32 *tgt, const u32 *lq, const u64 *loff, u64 max_shared, u32 bs,
+                                                   u32 bp, u32 n, const u64 *toff, u32 *otgt, u32 *osh) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < L; i += (u64)gridDim.x * blockDim.x) {
+        const u64 k = lkeys[i];
+        const u32 q = lq[k >> (bs + bp)];
+        const u64 r = i - loff[q];  // the slot's hits lie at [loff[q], ...), as emitted
+        if (r < n) {
+            const u64 o = toff[q] + r;
+            otgt[o] = tgt[off[q] + (k & ((1ULL << bp) - 1))];
+            osh[o] = (u32)(max_shared - ((k >> bp) & ((1ULL << bs) - 1)));
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_off_u32(const u64 *in, u64 n, u32 *out) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) out[i] = (u32)in[i];
+}
+
 unsigned grid_for(const bsk_ctx *ctx, u64 items, u64 per_block, u64 blocks_per_cu) {
     const u64 g = (items + per_block - 1) / per_block;
     return (unsigned)std::max<u64>(1, std::min<u64>(g, (u64)ctx->cus * blocks_per_cu));
@@ -414,13 +620,56 @@ extern "C" int bsk_sets_from_host(bsk_ctx *ctx, const uint64_t *offsets, uint64_
 
 extern "C" void bsk_index_release(bsk_index *ix) {
     if (!ix) return;
-    if (ix->ctx) (void)hipSetDevice(ix->ctx->device);
-    (void)hipFree(ix->keys);
-    (void)hipFree(ix->post_off);
-    (void)hipFree(ix->post_tgt);
-    (void)hipFree(ix->dir);
-    (void)hipFree(ix->tsize);
+    IndexArrays *a = ix->a;
+    if (a && a->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) {  // the last handle of this device's arrays
+        (void)hipSetDevice(a->device);
+        (void)hipFree(a->keys);
+        (void)hipFree(a->post_off);
+        (void)hipFree(a->post_tgt);
+        (void)hipFree(a->dir);
+        (void)hipFree(a->tsize);
+        delete a;
+    }
     delete ix;
+}
+
+extern "C" int bsk_index_attach(bsk_ctx *ctx, const bsk_index *ix, bsk_index **handle) {
+    if (handle) *handle = nullptr;
+    if (!ctx || !ix || !handle) return fail_arg(ctx, "bsk_index_attach: null argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    bsk_index *h = new (std::nothrow) bsk_index(*ix);
+    if (!h) return BSK_ERR_NOMEM;
+    h->ctx = ctx;
+    const IndexArrays *src = ix->a;
+    if (src->device == ctx->device) {  // same device: the arrays are shared
+        ix->a->refs.fetch_add(1, std::memory_order_relaxed);
+        *handle = h;
+        return BSK_OK;
+    }
+    h->a = new (std::nothrow) IndexArrays();  // another device: one copy of the arrays, owned by this handle (and those attached from it)
+    if (!h->a) {
+        delete h;
+        return BSK_ERR_NOMEM;
+    }
+    std::unique_ptr<bsk_index, void (*)(bsk_index *)> hold(h, bsk_index_release);
+    IndexArrays *d = h->a;
+    d->device = ctx->device;
+    const u64 U = ix->n_distinct, P = ix->n_postings, T = ix->n_targets, nb = 1ULL << ix->bits;
+    const size_t b_keys = (U ? U : 1) * 8, b_off = (U + 1) * 4, b_tgt = (P ? P : 1) * 4, b_dir = (nb + 1) * 4, b_ts = (T ? T : 1) * 4;
+    HIPCHK(ctx, hipMalloc(&d->keys, b_keys));
+    HIPCHK(ctx, hipMalloc(&d->post_off, b_off));
+    HIPCHK(ctx, hipMalloc(&d->post_tgt, b_tgt));
+    HIPCHK(ctx, hipMalloc(&d->dir, b_dir));
+    HIPCHK(ctx, hipMalloc(&d->tsize, b_ts));
+    // (the source arrays were complete when their build returned; the copies are complete when this returns)
+    HIPCHK(ctx, hipMemcpyPeer(d->keys, d->device, src->keys, src->device, b_keys));
+    HIPCHK(ctx, hipMemcpyPeer(d->post_off, d->device, src->post_off, src->device, b_off));
+    HIPCHK(ctx, hipMemcpyPeer(d->post_tgt, d->device, src->post_tgt, src->device, b_tgt));
+    HIPCHK(ctx, hipMemcpyPeer(d->dir, d->device, src->dir, src->device, b_dir));
+    HIPCHK(ctx, hipMemcpyPeer(d->tsize, d->device, src->tsize, src->device, b_ts));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    *handle = hold.release();
+    return BSK_OK;
 }
 
 extern "C" int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index **out) {
@@ -438,17 +687,20 @@ extern "C" int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index 
     if (!ix) return BSK_ERR_NOMEM;
     std::unique_ptr<bsk_index, void (*)(bsk_index *)> hold(ix, bsk_index_release);
     ix->ctx = ctx;
+    ix->a = new (std::nothrow) IndexArrays();
+    if (!ix->a) return BSK_ERR_NOMEM;
+    ix->a->device = ctx->device;
     ix->n_targets = T;
     ix->n_postings = P;
     Temps tmp;
     u64 *kin = nullptr, *kout = nullptr, *pos = nullptr, *part = nullptr, *tot = nullptr;
     u32 *tin = nullptr, *flag = nullptr;
-    HIPCHK(ctx, hipMalloc(&ix->post_tgt, (P ? P : 1) * 4));
-    HIPCHK(ctx, hipMalloc(&ix->tsize, (T ? T : 1) * 4));
+    HIPCHK(ctx, hipMalloc(&ix->a->post_tgt, (P ? P : 1) * 4));
+    HIPCHK(ctx, hipMalloc(&ix->a->tsize, (T ? T : 1) * 4));
     HIPCHK(ctx, tmp.get((void **)&tot, 64));
     HIPCHK(ctx, hipMemsetAsync(tot, 0, 64, st));
     if (T) {
-        hipLaunchKernelGGL(k_ix_sizes, dim3(grid_for(ctx, T, 256, 8)), dim3(256), 0, st, targets->offsets, T, ix->tsize);
+        hipLaunchKernelGGL(k_ix_sizes, dim3(grid_for(ctx, T, 256, 8)), dim3(256), 0, st, targets->offsets, T, ix->a->tsize);
         HIPCHK(ctx, hipGetLastError());
     }
     u64 U = 0;
@@ -459,10 +711,10 @@ extern "C" int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index 
         hipLaunchKernelGGL(k_ix_pairs, dim3(grid_for(ctx, P, 256, 16)), dim3(256), 0, st, targets->offsets, targets->values, T, P, kin, tin);
         HIPCHK(ctx, hipGetLastError());
         size_t tb = 0;
-        HIPCHK(ctx, rocprim::radix_sort_pairs(nullptr, tb, kin, kout, tin, ix->post_tgt, (size_t)P, 0, 64, st));
+        HIPCHK(ctx, rocprim::radix_sort_pairs(nullptr, tb, kin, kout, tin, ix->a->post_tgt, (size_t)P, 0, 64, st));
         void *stmp = nullptr;
         HIPCHK(ctx, tmp.get(&stmp, tb));
-        HIPCHK(ctx, rocprim::radix_sort_pairs(stmp, tb, kin, kout, tin, ix->post_tgt, (size_t)P, 0, 64, st));
+        HIPCHK(ctx, rocprim::radix_sort_pairs(stmp, tb, kin, kout, tin, ix->a->post_tgt, (size_t)P, 0, 64, st));
         flag = tin;  // (both free after the sort)
         pos = kin;
         HIPCHK(ctx, tmp.get((void **)&part, ((P + SCAN_CHUNK - 1) / SCAN_CHUNK + 2) * 8));
@@ -478,17 +730,17 @@ extern "C" int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index 
     const u64 nb = 1ULL << bits;
     ix->bits = bits;
     ix->n_distinct = U;
-    HIPCHK(ctx, hipMalloc(&ix->keys, (U ? U : 1) * 8));
-    HIPCHK(ctx, hipMalloc(&ix->post_off, (U + 1) * 4));
-    HIPCHK(ctx, hipMalloc(&ix->dir, (nb + 1) * 4));
+    HIPCHK(ctx, hipMalloc(&ix->a->keys, (U ? U : 1) * 8));
+    HIPCHK(ctx, hipMalloc(&ix->a->post_off, (U + 1) * 4));
+    HIPCHK(ctx, hipMalloc(&ix->a->dir, (nb + 1) * 4));
     if (P) {
-        hipLaunchKernelGGL(k_ix_scatter, dim3(grid_for(ctx, P, 256, 16)), dim3(256), 0, st, kout, flag, pos, P, ix->keys, ix->post_off);
+        hipLaunchKernelGGL(k_ix_scatter, dim3(grid_for(ctx, P, 256, 16)), dim3(256), 0, st, kout, flag, pos, P, ix->a->keys, ix->a->post_off);
         HIPCHK(ctx, hipGetLastError());
     } else {
-        HIPCHK(ctx, hipMemsetAsync(ix->post_off, 0, 4, st));
+        HIPCHK(ctx, hipMemsetAsync(ix->a->post_off, 0, 4, st));
     }
-    hipLaunchKernelGGL(k_ix_dir, dim3(grid_for(ctx, U + 1, 256, 16)), dim3(256), 0, st, ix->keys, U, bits, ix->dir);
-    hipLaunchKernelGGL(k_ix_maxb, dim3(grid_for(ctx, nb, 256, 8)), dim3(256), 0, st, ix->dir, nb, tot + 1);
+    hipLaunchKernelGGL(k_ix_dir, dim3(grid_for(ctx, U + 1, 256, 16)), dim3(256), 0, st, ix->a->keys, U, bits, ix->a->dir);
+    hipLaunchKernelGGL(k_ix_maxb, dim3(grid_for(ctx, nb, 256, 8)), dim3(256), 0, st, ix->a->dir, nb, tot + 1);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned + 1, tot + 1, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
@@ -577,7 +829,7 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
     HIPCHK(ctx, hipMemsetAsync(tot, 0, 64, st));  // [0] staging, [1] large target ids, [2] large queries, [3] large runs, [4] kept runs, [5] hits
     // A. lookups
     if (nq) {
-        hipLaunchKernelGGL(k_sr_lookup, dim3(grid_for(ctx, nq * 16, 256, 32)), dim3(256), 0, st, qs->offsets, qs->values, nq, ix->keys, ix->post_off, ix->dir,
+        hipLaunchKernelGGL(k_sr_lookup, dim3(grid_for(ctx, nq * 16, 256, 32)), dim3(256), 0, st, qs->offsets, qs->values, nq, ix->a->keys, ix->a->post_off, ix->a->dir,
                            ix->bits, rng, qsum);
         HIPCHK(ctx, hipGetLastError());
     }
@@ -593,7 +845,7 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
     u32 *st_tgt = static_cast<u32 *>(bst), *st_sh = st_tgt + (S ? S : 1);
     // C. queries of at most SR_CAP target ids
     if (nq) {
-        hipLaunchKernelGGL(k_sr_small, dim3(grid_for(ctx, nq, SR_WAVES, 40)), dim3(64 * SR_WAVES), 0, st, qs->offsets, rng, qsum, nq, ix->post_tgt, ix->tsize,
+        hipLaunchKernelGGL(k_sr_small, dim3(grid_for(ctx, nq, SR_WAVES, 40)), dim3(64 * SR_WAVES), 0, st, qs->offsets, rng, qsum, nq, ix->a->post_tgt, ix->a->tsize,
                            stage_off, thr, st_tgt, st_sh, hcnt);
         HIPCHK(ctx, hipGetLastError());
     }
@@ -608,7 +860,7 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
             *part2 = at<u64>(bl, o_part2);
         u32 *flag = at<u32>(bl, o_flag);
         hipLaunchKernelGGL(k_sr_list_large, dim3(grid_for(ctx, nq, 256, 8)), dim3(256), 0, st, qsum, nq, lslot, lq);
-        hipLaunchKernelGGL(k_lg_emit, dim3(grid_for(ctx, NL, 4, 16)), dim3(256), 0, st, qs->offsets, rng, lq, NL, loff, ix->post_tgt, lin);
+        hipLaunchKernelGGL(k_lg_emit, dim3(grid_for(ctx, NL, 4, 16)), dim3(256), 0, st, qs->offsets, rng, lq, NL, loff, ix->a->post_tgt, lin);
         HIPCHK(ctx, hipGetLastError());
         const unsigned end_bit = 32 + (NL > 1 ? 64 - __builtin_clzll(NL - 1) : 0);
         size_t tb = 0;
@@ -622,7 +874,7 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
         HIPCHK(ctx, scan_counts(st, KeepOf{flag}, L, part2, ridx, tot + 3, (u64 *)nullptr));
         hipLaunchKernelGGL(k_lg_runs, dim3(grid_for(ctx, L, 256, 16)), dim3(256), 0, st, flag, ridx, L, rstart);
         u32 *keep = flag;  // (free once the runs are known)
-        hipLaunchKernelGGL(k_lg_keep, dim3(grid_for(ctx, L, 256, 16)), dim3(256), 0, st, lout, rstart, ridx, L, lq, qs->offsets, ix->tsize, thr, keep, sfirst);
+        hipLaunchKernelGGL(k_lg_keep, dim3(grid_for(ctx, L, 256, 16)), dim3(256), 0, st, lout, rstart, ridx, L, lq, qs->offsets, ix->a->tsize, thr, keep, sfirst);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, scan_counts(st, KeepOf{keep}, L, part2, kpos, tot + 4, (u64 *)nullptr));
         hipLaunchKernelGGL(k_lg_place, dim3(grid_for(ctx, L, 256, 16)), dim3(256), 0, st, lout, rstart, ridx, L, keep, kpos, sfirst, lq, stage_off, st_tgt, st_sh,
@@ -646,6 +898,145 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
     res->n_large = NL;
     snprintf(res->plan, sizeof res->plan, "k_sr_lookup + k_sr_small (LDS sort, <= %d target ids per query); large path: %llu queries, %llu target ids",
              SR_CAP, (unsigned long long)NL, (unsigned long long)L);
+    return BSK_OK;
+}
+
+static int top_impl(bsk_ctx *ctx, const bsk_hits *h, u32 n, bsk_hits *res);
+extern "C" int bsk_hits_top(bsk_ctx *ctx, const bsk_hits *h, uint32_t n, bsk_hits **top) {
+    if (!ctx || !h || !top) return fail_arg(ctx, "bsk_hits_top: null argument");
+    if (h->ctx != ctx || (*top && (*top)->ctx != ctx)) return fail_arg(ctx, "bsk_hits_top: the hits belong to another context");
+    if (*top == h) return fail_arg(ctx, "bsk_hits_top: *top is h itself");
+    if (n == 0) return fail_arg(ctx, "bsk_hits_top: n == 0");
+    bsk_hits *res = *top;
+    *top = nullptr;
+    if (!res) res = new (std::nothrow) bsk_hits();
+    if (!res) return BSK_ERR_NOMEM;
+    res->ctx = ctx;
+    const int rc = top_impl(ctx, h, n, res);
+    if (rc != BSK_OK) {
+        bsk_hits_release(res);
+        return rc;
+    }
+    *top = res;
+    return BSK_OK;
+}
+
+static inline u32 bits_of(u64 x) { return x ? 64 - (u32)__builtin_clzll(x) : 0; }  // bits that hold 0 .. x
+
+static int top_impl(bsk_ctx *ctx, const bsk_hits *h, u32 n, bsk_hits *res) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const u64 nq = h->n_queries, Hin = h->n_hits;
+    const bool select = n <= TOP_SELECT_N;  // else: LDS sort, and the sort path beyond TOP_LDS_KEYS hits
+    auto grow = [&](void **p, size_t *cap, size_t bytes) -> hipError_t {
+        if (*cap >= bytes && *p) return hipSuccess;
+        (void)hipFree(*p);
+        *p = nullptr;
+        *cap = 0;
+        const size_t want = bytes + bytes / 4 + 256;
+        const hipError_t e = hipMalloc(p, want);
+        if (e == hipSuccess) *cap = want;
+        return e;
+    };
+    res->n_queries = nq;
+    res->n_hits = 0;
+    res->n_large = 0;
+    HIPCHK(ctx, grow((void **)&res->offsets, &res->c_offsets, (nq + 1) * 8));
+    // scratch: the search's own slots (its temporaries are dead once its hits exist)
+    Carve cq;
+    const size_t o_part = cq.add<u64>((nq + SCAN_CHUNK - 1) / SCAN_CHUNK + 2), o_tot = cq.add<u64>(8), o_lslot = cq.add<u64>(select ? 1 : nq + 1),
+                 o_loff = cq.add<u64>(select ? 1 : nq + 1), o_lq = cq.add<u32>(select ? 1 : nq);
+    void *bq = nullptr;
+    HIPCHK(ctx, pool_get(ctx, 10, cq.bytes, &bq));
+    u64 *part = at<u64>(bq, o_part), *tot = at<u64>(bq, o_tot), *lslot = at<u64>(bq, o_lslot), *loff = at<u64>(bq, o_loff);
+    u32 *lq = at<u32>(bq, o_lq);
+    // [0] hits kept, [1] hits of the sort path's queries, [2] those queries, [3] the most hits one of them has, [4] the largest shared count,
+    // [5] queries of the group kernel, [6] of the wave kernel
+    HIPCHK(ctx, hipMemsetAsync(tot, 0, 64, st));
+    HIPCHK(ctx, scan_counts(st, TopCnt{h->offsets, n}, nq, part, res->offsets, tot + 0, (u64 *)nullptr));
+    if (nq) {
+        hipLaunchKernelGGL(k_top_classes, dim3(grid_for(ctx, nq, 256, 8)), dim3(256), 0, st, h->offsets, nq, select ? ~0ULL : (u64)TOP_LDS_KEYS, tot + 5);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (!select) {
+        HIPCHK(ctx, scan_counts(st, TopLargeOf{h->offsets, false}, nq, part, loff, tot + 1, tot + 3));
+        HIPCHK(ctx, scan_counts(st, TopLargeOf{h->offsets, true}, nq, part, lslot, tot + 2, (u64 *)nullptr));
+        if (Hin) {
+            hipLaunchKernelGGL(k_top_maxshared, dim3(grid_for(ctx, Hin, 256, 8)), dim3(256), 0, st, h->shared, Hin, tot + 4);
+            HIPCHK(ctx, hipGetLastError());
+        }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 56, hipMemcpyDeviceToHost, st));  // the one read-back
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const u64 H = ctx->h_pinned[0], L = ctx->h_pinned[1], NL = ctx->h_pinned[2], maxc = ctx->h_pinned[3], maxs = ctx->h_pinned[4], n_group = ctx->h_pinned[5],
+              n_wave = ctx->h_pinned[6];
+    HIPCHK(ctx, grow((void **)&res->target, &res->c_target, (H ? H : 1) * 4));
+    HIPCHK(ctx, grow((void **)&res->shared, &res->c_shared, (H ? H : 1) * 4));
+    if (n_group) {
+        hipLaunchKernelGGL(k_top_group, dim3(grid_for(ctx, nq * 16, 256, 32)), dim3(256), 0, st, h->offsets, h->target, h->shared, nq, n, res->offsets, res->target,
+                           res->shared);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (n_wave) {
+        // queries a wavefront looks at per step: one while there are fewer queries than wavefronts (a genome query each), 64 at read scale
+        const u64 waves = (u64)ctx->cus * 8 * TOP_WAVES;
+        u32 qb = 1;
+        while (qb < 64 && (u64)qb * waves < nq) qb <<= 1;
+        const unsigned grid = grid_for(ctx, (nq + qb - 1) / qb, TOP_WAVES, 8);
+        if (select)
+            hipLaunchKernelGGL(k_top_select, dim3(grid), dim3(64 * TOP_WAVES), 0, st, h->offsets, h->target, h->shared, nq, n, qb, res->offsets, res->target, res->shared);
+        else
+            hipLaunchKernelGGL(k_top_lds, dim3(grid), dim3(64 * TOP_WAVES), 0, st, h->offsets, h->target, h->shared, nq, n, qb, res->offsets, res->target, res->shared);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (NL) {
+        const u32 bs = bits_of(maxs), bp = bits_of(maxc - 1), bslot = bits_of(NL - 1);
+        if (bs + bp + bslot > 63) {
+            ctx->err = "bsk_hits_top: the sort path's key (query slot, shared count, hit) needs more than 63 bits (split the queries)";
+            return BSK_ERR_UNSUPPORTED;
+        }
+        Carve cl;
+        const size_t o_in = cl.add<u64>(L), o_out = cl.add<u64>(L);
+        void *bl = nullptr, *stmp = nullptr;
+        HIPCHK(ctx, pool_get(ctx, 30, cl.bytes, &bl));
+        u64 *lin = at<u64>(bl, o_in), *lout = at<u64>(bl, o_out);
+        hipLaunchKernelGGL(k_top_list, dim3(grid_for(ctx, nq, 256, 8)), dim3(256), 0, st, h->offsets, nq, lslot, lq);
+        hipLaunchKernelGGL(k_top_emit, dim3(grid_for(ctx, NL, 4, 16)), dim3(256), 0, st, h->offsets, h->shared, lq, NL, loff, maxs, bs, bp, lin);
+        HIPCHK(ctx, hipGetLastError());
+        size_t tb = 0;
+        HIPCHK(ctx, sets_sort_u64(nullptr, tb, lin, lout, (size_t)L, 0, bs + bp + bslot, st));
+        HIPCHK(ctx, pool_get(ctx, 31, tb ? tb : 8, &stmp));
+        HIPCHK(ctx, sets_sort_u64(stmp, tb, lin, lout, (size_t)L, 0, bs + bp + bslot, st));
+        hipLaunchKernelGGL(k_top_place, dim3(grid_for(ctx, L, 256, 16)), dim3(256), 0, st, lout, L, h->offsets, h->target, lq, loff, maxs, bs, bp, n, res->offsets,
+                           res->target, res->shared);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    res->n_hits = H;
+    res->n_large = NL;
+    snprintf(res->plan, sizeof res->plan, "bsk_hits_top n = %u: k_top_group %llu queries (<= %d hits); %s %llu queries; sort path: %llu queries, %llu hits", n,
+             (unsigned long long)n_group, TOP_GROUP, select ? "k_top_select" : "k_top_lds", (unsigned long long)n_wave, (unsigned long long)NL,
+             (unsigned long long)L);
+    return BSK_OK;
+}
+
+int hits_fetch_narrow(bsk_ctx *ctx, const bsk_hits *h, uint32_t *offsets, uint32_t *target, uint32_t *shared, uint64_t hit_cap) {
+    if (!ctx || !h || !offsets || !target || !shared) return fail_arg(ctx, "hits_fetch_narrow: null argument");
+    if (h->ctx != ctx) return fail_arg(ctx, "hits_fetch_narrow: the hits belong to another context");
+    if (h->n_hits > hit_cap) return fail_arg(ctx, "hits_fetch_narrow: hit_cap too small");
+    if (h->n_hits >= (1ULL << 32)) return BSK_ERR_UNSUPPORTED;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    void *o32 = nullptr;
+    const size_t need = (h->n_queries + 1) * 4;
+    HIPCHK(ctx, pool_get(ctx, 20, need, &o32));  // (bsk_sets_fetch_narrow's slot: both use it between two synchronisations of the stream)
+    hipLaunchKernelGGL(k_off_u32, dim3(grid_for(ctx, h->n_queries + 1, 256, 8)), dim3(256), 0, ctx->stream, h->offsets, h->n_queries + 1, (u32 *)o32);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(offsets, o32, need, hipMemcpyDeviceToHost, ctx->stream));
+    if (h->n_hits) {
+        HIPCHK(ctx, hipMemcpyAsync(target, h->target, h->n_hits * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(shared, h->shared, h->n_hits * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return BSK_OK;
 }
 

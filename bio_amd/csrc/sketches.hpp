@@ -208,6 +208,9 @@ class SearchHits : public Owned<bsk_hits, bsk_hits_release> {
         bsk_hits_plan(p_, nullptr, &n);
         return n;
     }
+    // every query's min(n, hits) best hits, largest shared count first, ties by ascending target (bsk_hits_top); into: empty, or the
+    // result of an earlier top on this engine (its device arrays are kept and only grow)
+    int top(Engine &e, uint32_t n, SearchHits &into) const { return bsk_hits_top(e.ctx(), p_, n, &into.handle()); }
 };
 
 // inverted index of target sets (bsk_index)
@@ -227,7 +230,52 @@ class SearchIndex : public Owned<bsk_index, bsk_index_release> {
         bsk_index_info(p_, nullptr, nullptr, nullptr, &m, nullptr);
         return m;
     }
+    // a handle on this index for another engine (bsk_index_attach): shared arrays on the same device, one copy on another; the handles
+    // of an index may go in any order
+    int attach(Engine &e, SearchIndex &handle) const {
+        bsk_index_release(handle.p_);
+        handle.p_ = nullptr;
+        return bsk_index_attach(e.ctx(), p_, &handle.p_);
+    }
 };
+
+// One chunk of a BSK_SINK_HITS pipeline: record i owns target / shared[offset(i) .. offset(i + 1)); valid inside the callback.
+struct HitsChunk {
+    const bsk_chunk *c = nullptr;
+    const uint32_t *target = nullptr, *shared = nullptr;
+    uint64_t offset(uint64_t i) const { return c->offsets32 ? c->offsets32[i] : c->offsets64[i]; }
+};
+// Reads in host memory in, every read's best targets out (bsk_pipeline_open_memory_search): on_chunk(const HitsChunk &) sees every
+// chunk in input order.  ix may belong to any engine; it must have been built from sets of the same params and scale.
+template <class F>
+int classify_memory(const std::vector<int> &devices, int n_streams, uint64_t chunk_records, int sets_scale, const uint8_t *bytes, const uint64_t *offsets, uint64_t n,
+                    const bsk_params &p, const SearchIndex &ix, const bsk_search_params &sp, uint32_t top_n, F &&on_chunk, bsk_pipeline_stats *stats = nullptr) {
+    bsk_pipeline_config cfg{};
+    cfg.devices = devices.data();
+    cfg.n_devices = (int32_t)devices.size();
+    cfg.n_streams = n_streams;
+    cfg.chunk_records = chunk_records;
+    cfg.sink = BSK_SINK_HITS;
+    cfg.sets_scale = sets_scale;
+    cfg.alphabet = BSK_ALPHA_DNA;
+    const bsk_pipeline_search s{ix.get(), sp, top_n, 0};
+    bsk_pipeline *pl = nullptr;
+    int rc = bsk_pipeline_open_memory_search(&cfg, bytes, offsets, n, 1, &p, &s, &pl);
+    if (rc != BSK_OK) return rc;
+    for (;;) {
+        const bsk_chunk *c = nullptr;
+        rc = bsk_pipeline_next(pl, &c);
+        if (rc != BSK_OK || !c) break;
+        HitsChunk hc;
+        hc.c = c;
+        rc = bsk_chunk_hits(c, &hc.target, &hc.shared);
+        if (rc == BSK_OK) on_chunk(hc);
+        bsk_pipeline_release(pl, c);
+        if (rc != BSK_OK) break;
+    }
+    const int crc = bsk_pipeline_close(pl, stats);
+    return rc != BSK_OK ? rc : crc;
+}
 
 inline Engine &default_engine() {
     static Engine e(0);

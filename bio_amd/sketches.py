@@ -326,6 +326,13 @@ class Index:
         res._bind(h, np.diff(queries.offsets()), self.target_sizes)
         return res
 
+    def attach(self, engine: "Engine") -> "Index":
+        """A handle on this index for another engine (bsk_index_attach): on the same device the arrays are shared, on another device
+        they are copied there once.  Search it through the returned Index; the two may be closed in any order."""
+        h = C.c_void_p()
+        engine._chk(engine.lib.bsk_index_attach(engine.ctx, self.h, C.byref(h)))
+        return Index(engine, h, self.target_sizes)
+
     def close(self):
         if self.h:
             self.eng.lib.bsk_index_release(self.h)
@@ -359,6 +366,18 @@ class Hits:
         p, n = C.c_char_p(), C.c_uint64()
         self.eng._chk(self.eng.lib.bsk_hits_plan(self.h, C.byref(p), C.byref(n)))
         return dict(plan=(p.value or b"").decode(), n_large_queries=n.value)
+
+    def top(self, n: int, reuse: Optional["Hits"] = None) -> "Hits":
+        """Every query's min(n, hits) best hits, largest shared count first, ties by ascending target (bsk_hits_top) -> Hits.
+        reuse: the Hits of an earlier top() on this engine, whose device arrays are kept."""
+        h = reuse.h if reuse is not None and reuse.h else C.c_void_p()
+        rc = self.eng.lib.bsk_hits_top(self.eng.ctx, self.h, n, C.byref(h))
+        if reuse is not None:
+            reuse.h = h if h.value else None  # (kept on an argument error, released by the library on any other)
+        self.eng._chk(rc)
+        res = reuse if reuse is not None else Hits(self.eng)
+        res._bind(h, self.query_sizes, self.target_sizes)
+        return res
 
     def device(self):
         """bsk_hits_device -> (offsets_ptr, target_ptr, shared_ptr)"""
@@ -522,9 +541,17 @@ class Engine:
     @staticmethod
     def pipeline_open(params, *, paths=None, data: np.ndarray = None, offsets: np.ndarray = None, devices=(0,), n_streams: int = 2,
                       chunk_records: int = 1 << 18, sink: int = L.SINK_TUPLES, sets_scale: int = 1, alphabet: int = -1, repeat: int = 1,
-                      host_checksum: bool = False, n_readers: int = 0) -> "Pipeline":
-        """bsk_pipeline_open_fastx / _memory: the pipeline with a consumer (the role of fastx's ChunkChan, seqio/fastx/reader.go:562-608)."""
-        return Pipeline(params, paths, data, offsets, devices, n_streams, chunk_records, sink, sets_scale, alphabet, repeat, host_checksum, n_readers)
+                      host_checksum: bool = False, n_readers: int = 0, search: Optional["Index"] = None, top_n: int = 0, min_shared: int = 1,
+                      min_query_cov: float = 0.0, min_target_cov: float = 0.0) -> "Pipeline":
+        """bsk_pipeline_open_fastx / _memory: the pipeline with a consumer (the role of fastx's ChunkChan, seqio/fastx/reader.go:562-608).
+        search=index (with sink=SINK_HITS): bsk_pipeline_open_*_search -- every chunk's per-record sets (sets_scale) are searched against
+        the index on the device and the chunks carry hits (ChunkView.target / .shared), every read's top_n best when top_n != 0.  The
+        index must have been built from sets of the same params and scale, and stay open until the pipeline is closed."""
+        sp = None
+        if search is not None:
+            sp = L.PipelineSearch(search.h.value if isinstance(search.h, C.c_void_p) else search.h, L.SearchParams(min_shared, 0, min_query_cov, min_target_cov),
+                                  top_n, 0)
+        return Pipeline(params, paths, data, offsets, devices, n_streams, chunk_records, sink, sets_scale, alphabet, repeat, host_checksum, n_readers, sp, search)
 
     @staticmethod
     def pipeline_trim() -> None:
@@ -770,6 +797,11 @@ class ChunkView:
         self.pos16 = view(c.pos16, nv, np.uint16) if nv else None   # BSK_POS16 encoding (bit 15 = strand), as delivered
         self.pos32 = view(c.pos32, nv, np.uint32) if nv else None   # BSK_POS encoding (bit 31 = strand): chunks with a read of 32 768 bases or more
         self._pos = self._strand = None
+        self.target = self.shared = None  # SINK_HITS: record i owns target / shared[offsets[i] : offsets[i + 1]] (bsk_chunk_hits)
+        if c.sink == L.SINK_HITS:
+            pt, ps = C.c_void_p(), C.c_void_p()
+            if L.load().bsk_chunk_hits(C.byref(c), C.byref(pt), C.byref(ps)) == L.OK:
+                self.target, self.shared = view(pt.value, nv, np.uint32), view(ps.value, nv, np.uint32)
 
     @property
     def pos(self):
@@ -804,20 +836,30 @@ class Pipeline:
         pl.stats
     """
 
-    def __init__(self, params, paths, data, offsets, devices, n_streams, chunk_records, sink, sets_scale, alphabet, repeat, host_checksum, n_readers):
+    def __init__(self, params, paths, data, offsets, devices, n_streams, chunk_records, sink, sets_scale, alphabet, repeat, host_checksum, n_readers,
+                 search=None, index=None):
         self.lib = L.load()
         self._dev = (C.c_int * len(devices))(*devices)
         cfg = L.PipelineConfig(self._dev, len(devices), n_streams, chunk_records, sink, sets_scale, alphabet, 1 if host_checksum else 0, n_readers, 0)
         self.h = C.c_void_p()
         self._keep = (data, offsets, params)
+        self._index = index  # (the searched index lives at least as long as the pipeline)
         if paths is not None:
             arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
-            rc = self.lib.bsk_pipeline_open_fastx(C.byref(cfg), arr, len(paths), C.byref(params), C.byref(self.h))
+            if search is not None:
+                rc = self.lib.bsk_pipeline_open_fastx_search(C.byref(cfg), arr, len(paths), C.byref(params), C.byref(search), C.byref(self.h))
+            else:
+                rc = self.lib.bsk_pipeline_open_fastx(C.byref(cfg), arr, len(paths), C.byref(params), C.byref(self.h))
         else:
             data = np.ascontiguousarray(data, dtype=np.uint8)
             offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
             self._keep = (data, offsets, params)
-            rc = self.lib.bsk_pipeline_open_memory(C.byref(cfg), data.ctypes.data, offsets.ctypes.data, len(offsets) - 1, repeat, C.byref(params), C.byref(self.h))
+            if search is not None:
+                rc = self.lib.bsk_pipeline_open_memory_search(C.byref(cfg), data.ctypes.data, offsets.ctypes.data, len(offsets) - 1, repeat, C.byref(params),
+                                                              C.byref(search), C.byref(self.h))
+            else:
+                rc = self.lib.bsk_pipeline_open_memory(C.byref(cfg), data.ctypes.data, offsets.ctypes.data, len(offsets) - 1, repeat, C.byref(params),
+                                                       C.byref(self.h))
         if rc != L.OK:
             self.h = C.c_void_p()
             raise _SENTINELS.get(rc) or DeviceError(f"bsk_pipeline_open: {self.lib.bsk_err_name(rc).decode()}")

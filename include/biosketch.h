@@ -524,6 +524,54 @@ int bsk_hits_fetch(bsk_ctx *ctx, const bsk_hits *h, uint64_t first, uint64_t cou
 int bsk_hits_device(const bsk_hits *h, const uint64_t **offsets, const uint32_t **target, const uint32_t **shared);
 void bsk_hits_release(bsk_hits *h);
 
+/* ---- classifying reads: an index several contexts search, the n best hits of a query, the pipeline's hits sink ------------------
+ * A handle on ix for another context.  Same device as ix: the device arrays are shared (reference counted, read-only);
+ * another device: the arrays are copied there once.  The handle is searched with bsk_index_search(ctx, handle, ...) and
+ * released with bsk_index_release; a device's arrays go when their last handle goes, in any release order (the index
+ * bsk_index_build returned is one handle among the others: it may be released while attached handles live).
+ * bsk_index_info works on a handle and reports the same numbers.  A handle may be attached from a handle.
+ * The index is read-only during a search and every scratch array is the searching context's own, so several contexts may
+ * search their handles of one index at the same time from several threads.  A release must not overlap a search ON THAT
+ * SAME HANDLE (nor an attach from it); releases and searches of different handles need no ordering. */
+int bsk_index_attach(bsk_ctx *ctx, const bsk_index *ix, bsk_index **handle);
+
+/* For every query of h the min(n, its hit count) hits with the largest shared count (for one query that is the order of
+ * containment shared/|q|), ties by ascending target id; inside a query they are stored in that order (NOT ascending by
+ * target as bsk_index_search stores them).  *top: NULL or the object of an earlier call on this context (arrays kept,
+ * grow only; error rules as bsk_index_search); *top == h is BSK_ERR_ARG.  n == 0 is BSK_ERR_ARG.  The result is an
+ * ordinary bsk_hits: _info / _fetch / _device / _release work on it; bsk_hits_plan describes what ran (queries of at most
+ * 16 hits: a group of 16 lanes each; more hits and n <= 16: n rounds of a wave-wide maximum; n > 16: a sort in LDS up to
+ * 1 024 hits, beyond that one device-wide key sort -- bsk_hits_plan's count is the queries of that last path).
+ * Everything runs on the context's stream; the host reads back one block of sizes.  The key of the sort path holds
+ * (queries on that path) x (largest shared count) x (most hits of one query): beyond 63 bits -- far past what device
+ * memory holds -- the call is BSK_ERR_UNSUPPORTED. */
+int bsk_hits_top(bsk_ctx *ctx, const bsk_hits *h, uint32_t n, bsk_hits **top);
+
+/* BSK_SINK_HITS: reads in, the best targets of every read out.  Per chunk a worker sketches, reduces the result to per-record sets
+ * (bsk_result_sets_reuse, cfg->sets_scale), searches them on its own handle of s->index (bsk_index_search with s->params) and, for
+ * top_n != 0, keeps every read's top_n best (bsk_hits_top); the sets never leave the device.  A chunk's offsets32 (offsets64 from 2^32
+ * hits) are the records' hit offsets, n_values the number of hits, hash == NULL; bsk_chunk_hits gives target[] and shared[] (valid
+ * until the chunk is released).  link_bytes is n_records * 5 + n_hits * 8 in the narrow form; with host_checksum, checksum is the sum
+ * of target + shared over the hits.  next / release / close / cancel / run, the record order, status[] and the statistics are those of
+ * the other sinks.  cfg->sink must be BSK_SINK_HITS for these two entries, and BSK_SINK_HITS is BSK_ERR_ARG in bsk_pipeline_open_fastx
+ * / _memory.  s->index may belong to any context and any device: the pipeline attaches a handle per worker (one copy per further
+ * device) and releases them when it closes; the caller may release s->index only after bsk_pipeline_close.
+ * The index must have been built from sets of the same bsk_params and the same scale as p and cfg->sets_scale: the pipeline cannot
+ * check that, and hits against an index of other parameters are meaningless. */
+enum { BSK_SINK_HITS = 3 };
+typedef struct bsk_pipeline_search {
+    const bsk_index *index;     /* of any context; the pipeline attaches a handle per worker (one copy per further device) */
+    bsk_search_params params;
+    uint32_t top_n;             /* 0: every hit, targets ascending; n: bsk_hits_top order */
+    uint32_t reserved;          /* 0 */
+} bsk_pipeline_search;
+int bsk_pipeline_open_fastx_search(const bsk_pipeline_config *cfg, const char *const *paths, int n_paths, const bsk_params *p,
+                                   const bsk_pipeline_search *s, bsk_pipeline **out);
+int bsk_pipeline_open_memory_search(const bsk_pipeline_config *cfg, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, int repeat,
+                                    const bsk_params *p, const bsk_pipeline_search *s, bsk_pipeline **out);
+/* BSK_SINK_HITS chunks: offsets32 / offsets64 are the records' hit offsets, n_values the number of hits, hash == NULL */
+int bsk_chunk_hits(const bsk_chunk *c, const uint32_t **target, const uint32_t **shared);
+
 #ifdef __cplusplus
 }
 #endif
