@@ -20,7 +20,7 @@ void dense_minimizer_launch(int w, int grid, hipStream_t stream, const KArgs &a)
 void dense_minimizer_ascii_launch(int w, int grid, hipStream_t stream, const KArgs &a);  // the ASCII side launch of a mixed batch (KArgs::subset, ascii, aoff, out_base)
 int dense_minimizer_ascii_blocks_per_cu(int w);
 
-bool pk_minimizer_supported(int w);  // packed 32-bit window machine, w <= 16 (kernels_pk.hpp)
+bool pk_minimizer_supported(int w);  // packed 32-bit window machine, w = 2..13 (kernels_pk.hpp)
 int pk_minimizer_blocks_per_cu(int w);
 u32 pk_minimizer_short_bases();
 void pk_minimizer_launch(int w, bool long_reads, int grid, hipStream_t stream, const KArgs &a);

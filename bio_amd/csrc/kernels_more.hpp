@@ -119,7 +119,8 @@ static __global__ __launch_bounds__(64) void k_prot_minimizer(KArgs a) {
             src.init(a.ascii, off, L, a.k);
             window_pass<WySrc, CAP, true>(src, nk, nk_max, W, ring_h, ring_p, lane, st, c2, t2, a.hash, a.pos, base + excl);
         }
-        if (r < a.n) a.status[r] = (u8)((ok ? BSK_ST_OK : BSK_ST_SHORT) | ((tie && ok) ? BSK_ST_FIRST_WINDOW_TIE : 0));
+        // (nk == 0 with ok: a translation with fewer than w k-mers -- no window, nothing to flag; the lane's padding hashes are all 0 and looked like a tie)
+        if (r < a.n) a.status[r] = (u8)((ok ? BSK_ST_OK : BSK_ST_SHORT) | ((tie && ok && nk) ? BSK_ST_FIRST_WINDOW_TIE : 0));
     }
 }
 

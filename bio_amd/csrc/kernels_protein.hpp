@@ -403,7 +403,9 @@ __global__ __launch_bounds__(64) void k_prot_minimizer_fast(KArgs a) {
                     }
                 }
             }
-            tie = (u32)((fp.tm >> lane) & 1);
+            // (a DNA-fed lane may pass the nucleotide length check with a translation of fewer than W k-mers: no window, nothing to flag --
+            // its padding hashes are all equal and looked like a tie)
+            tie = nk ? (u32)((fp.tm >> lane) & 1) : 0u;
         }
         if (r < a.n) {
             a.refs[r] = ((ubase + (u64)lane * slab_read) << 24) | done;

@@ -328,7 +328,7 @@ int make_plan_enc(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, Plan &p
             pl.bin_gran = bin_gran_for(ctx, b, p->w);
             per_cu = dense_minimizer_blocks_per_cu(p->w);
         } else if (!use_ascii && pk_minimizer_supported(p->w) && b->maxlen < 32768u && !ctx->opt.force_generic && !ctx->opt.no_pk && !ctx->no_syn_pk) {
-            pl.which = K_MIN_PK;  // w <= 16: packed 32-bit window machine (kernels_pk.hpp)
+            pl.which = K_MIN_PK;  // w = 2..13: packed 32-bit window machine (kernels_pk.hpp)
             pl.fast_w = p->w;
             pl.fast_k = b->maxlen > pk_minimizer_short_bases() ? 1 : 0;  // (the kernel's LONG argument, for plan_name)
             pl.slab = true;

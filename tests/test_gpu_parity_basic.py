@@ -13,9 +13,20 @@ def rand_dna(rng, n, alpha="ACGT"):
     return "".join(rng.choice(alpha) for _ in range(n))
 
 
-def check_minimizer(engine, oracle, seqs, k, w, circular=False):
+FAST_ONLY = ("BSK_NO_RING", "BSK_NO_DENSE", "BSK_NO_PK")  # barred from every packed and per-read-slab kernel: k_minimizer_fast<W> for W <= 16 too
+DENSE_ONLY = ("BSK_NO_RING", "BSK_NO_PKD")                # ... from the unit-row and the packed per-read-slab kernel: k_minimizer_dense<W>
+
+
+def plan_is(got, want):
+    """exact, or (a name that ends in a comma) exact up to the template arguments that follow"""
+    return got.startswith(want) if want.endswith(",") else got == want
+
+
+def check_minimizer(engine, oracle, seqs, k, w, circular=False, plan=None):
     b = engine.batch(seqs)
     res = engine.run(b, engine.params(L.MINIMIZER, k, w=w, circular=circular))
+    if plan is not None:
+        assert plan_is(res.plan()["kernel"], plan), (res.plan(), plan, k, w)
     for i, s in enumerate(seqs):
         st, h, p = res.read(i)
         try:
@@ -84,32 +95,42 @@ def test_minimizer_circular(engine, oracle):
     check_minimizer(engine, oracle, seqs, 7, 4, circular=True)
 
 
-def test_minimizer_overflow_of_lds_staging(engine, oracle):
-    # strictly "decreasing" runs force > 32 selections per read -> exercises the direct re-run path
+def test_minimizer_overflow_of_lds_staging(engine, oracle, monkeypatch):
+    # strictly "decreasing" runs force > 32 selections per read -> exercises the direct re-run path of k_minimizer_fast's LDS staging
+    # (as planned today these batches run on the per-read-slab kernels; the switches put w = 2 back on k_minimizer_fast)
     rng = random.Random(11)
     seqs = [rand_dna(rng, 400) for _ in range(70)]
-    check_minimizer(engine, oracle, seqs, 9, 2)
-    check_minimizer(engine, oracle, seqs, 15, 1)
+    check_minimizer(engine, oracle, seqs, 9, 2, plan="k_minimizer_pkd<2>")
+    check_minimizer(engine, oracle, seqs, 15, 1, plan="k_minimizer_dense<1>")
+    for name in FAST_ONLY:
+        monkeypatch.setenv(name, "1")
+    check_minimizer(engine, oracle, seqs, 9, 2, plan="k_minimizer_fast<2,")
 
 
 def test_minimizer_paired_staging_columns(engine, oracle, monkeypatch):
     """k_minimizer_fast stages lanes l and l+32 in one LDS column filled from both ends: columns that overflow because of
-    their SUM, lanes that run out of the column alone (both directions), and one-sided columns (BSK_NO_DENSE keeps these
-    batches on that kernel)."""
-    monkeypatch.setenv("BSK_NO_DENSE", "1")
-    rng = random.Random(56)
-    seqs = [rand_dna(rng, rng.randint(150, 330)) for _ in range(200)]  # 22..52 tuples per read: some column sums reach 56, some do not
-    check_minimizer(engine, oracle, seqs, 21, 11)
-    seqs = [rand_dna(rng, 150) for _ in range(128)]
-    for lane in (3, 45, 64 + 31, 64 + 32):  # ~150 tuples: beyond the whole column, upwards (lane < 32) and downwards
-        seqs[lane] = rand_dna(rng, 900)
-    check_minimizer(engine, oracle, seqs, 21, 11)
-    for lo, hi in ((10, 280), (280, 10), (0, 330), (330, 25)):  # one lane of every column (nearly) empty, the other up to ~48 tuples
-        seqs = [rand_dna(rng, lo if (i & 32) == 0 else hi) for i in range(192)]
-        check_minimizer(engine, oracle, seqs, 21, 11)
-    seqs = [rand_dna(rng, rng.choice([150, 151, 170, 200])) for _ in range(700)]  # several tickets, ragged, w > 16 too
-    for k, w in ((21, 11), (31, 15), (15, 20), (25, 32)):
-        check_minimizer(engine, oracle, seqs, k, w)
+    their SUM, lanes that run out of the column alone (both directions), and one-sided columns.  k_minimizer_fast<W <= 13> is what every
+    k_minimizer_pk / _ring / _pkd call re-plans to when its list of reads for the exact machine fills.
+    Every batch runs twice.  With BSK_NO_DENSE alone, as this test was written: since the unit-row and the packed kernels were added
+    that switch leaves the w = 11 batches on k_minimizer_ring / k_minimizer_pk, whose pairs of columns are filled the same way (only the
+    w = 15, 20 and 32 calls still reach k_minimizer_fast).  Then with BSK_NO_RING + BSK_NO_DENSE + BSK_NO_PK, which plan
+    k_minimizer_fast<W> for every W: asserted by name."""
+    for env, fast_11 in ((("BSK_NO_DENSE",), None), (FAST_ONLY, "k_minimizer_fast<11,")):
+        for name in env:
+            monkeypatch.setenv(name, "1")
+        rng = random.Random(56)
+        seqs = [rand_dna(rng, rng.randint(150, 330)) for _ in range(200)]  # 22..52 tuples per read: some column sums reach 56, some do not
+        check_minimizer(engine, oracle, seqs, 21, 11, plan=fast_11)
+        seqs = [rand_dna(rng, 150) for _ in range(128)]
+        for lane in (3, 45, 64 + 31, 64 + 32):  # ~150 tuples: beyond the whole column, upwards (lane < 32) and downwards
+            seqs[lane] = rand_dna(rng, 900)
+        check_minimizer(engine, oracle, seqs, 21, 11, plan=fast_11)
+        for lo, hi in ((10, 280), (280, 10), (0, 330), (330, 25)):  # one lane of every column (nearly) empty, the other up to ~48 tuples
+            seqs = [rand_dna(rng, lo if (i & 32) == 0 else hi) for i in range(192)]
+            check_minimizer(engine, oracle, seqs, 21, 11, plan=fast_11)
+        seqs = [rand_dna(rng, rng.choice([150, 151, 170, 200])) for _ in range(700)]  # several tickets, ragged, w > 16 too
+        for k, w in ((21, 11), (31, 15), (15, 20), (25, 32)):
+            check_minimizer(engine, oracle, seqs, k, w, plan=fast_11 if w == 11 else "k_minimizer_fast<%d," % w)
 
 
 @pytest.mark.parametrize("k,canonical,circular", [(21, True, False), (21, False, False), (10, True, True), (1, True, False),
@@ -120,6 +141,11 @@ def test_nthash_stream(engine, oracle, k, canonical, circular):
     seqs += ["", "A" * 200, rand_dna(rng, 150, "ACGTN")]
     b = engine.batch(seqs)
     res = engine.run(b, engine.params(L.NTHASH, k, canonical=canonical, circular=circular))
+    # the stream kernel takes 512 bases -- a circular read with its k - 1 appended bases and k more of room --, the read with an N goes to the
+    # ASCII side launch; beyond that the whole batch runs on the general ASCII kernel
+    planned = max(len(s) for s in seqs) + ((k - 1 if k > 1 else 0) + k if circular else 0)
+    want = "k_nthash_fast<%d> + ASCII side launch" % int(canonical) if planned <= 512 else "k_nthash_stream<1>"
+    assert res.plan()["kernel"] == want, (res.plan(), want, planned)
     for i, s in enumerate(seqs):
         st, h, _ = res.read(i)
         try:
@@ -207,14 +233,28 @@ def test_degenerate_batches(engine):
 
 
 @pytest.mark.parametrize("k,w", [(21, 2), (21, 5), (15, 8), (31, 4)])
-def test_dense_minimizers_and_their_fallback(engine, oracle, k, w):
+def test_dense_minimizers_and_their_fallback(engine, oracle, monkeypatch, k, w):
     """Small windows select more than 32 positions per 150-bp read: the per-read-slab kernel (k_minimizer_dense) flushes
-    mid-read; a low-complexity read (a new minimizer at every position) outgrows its slab and makes the call re-plan."""
+    mid-read; a low-complexity read (a new minimizer at every position) outgrows its slab and makes the call re-plan.
+    As planned today (the first three calls) these batches run on the unit-row / packed per-read-slab kernels, which leave such a read to
+    the exact machine; BSK_NO_RING + BSK_NO_PKD put them back on k_minimizer_dense<W>, by name, and its re-plan ends on k_minimizer_fast<W>."""
     rng = random.Random(k * 7 + w)
     seqs = [rand_dna(rng, rng.choice([150, 150, 250, rng.randint(1, 300)])) for _ in range(300)]
-    check_minimizer(engine, oracle, seqs, k, w)                                   # dense kernel
-    check_minimizer(engine, oracle, seqs + ["A" * 250, "AC" * 100], k, w)        # slab overflow -> re-plan
-    check_minimizer(engine, oracle, seqs + [rand_dna(rng, 200, "ACGTN")], k, w)  # mixed: dense main launch + ASCII side launch
+    mixed = seqs + [rand_dna(rng, 200, "ACGTN")]
+    check_minimizer(engine, oracle, seqs, k, w)
+    check_minimizer(engine, oracle, seqs + ["A" * 250, "AC" * 100], k, w)
+    check_minimizer(engine, oracle, mixed, k, w)
+    for name in DENSE_ONLY:
+        monkeypatch.setenv(name, "1")
+    check_minimizer(engine, oracle, seqs, k, w, plan="k_minimizer_dense<%d>" % w)                              # dense kernel
+    # a read's slab holds 2.6 / (w + 1) of the longest read's windows + 16 tuples, in whole lines of 16 (make_plan_enc); the poly-A read selects
+    # every one of its windows: beyond its slab the call re-plans (at w = 2 the slab still takes it)
+    nwin = max(len(q) for q in seqs + ["A" * 250]) - k - w + 2
+    slab = (min(nwin, int(nwin * 2.6 / (w + 1.0)) + 16) + 15) & ~15
+    replans = 250 - k - w + 2 > slab
+    assert replans == (w != 2)
+    check_minimizer(engine, oracle, seqs + ["A" * 250, "AC" * 100], k, w, plan="k_minimizer_fast<%d," % w if replans else "k_minimizer_dense<%d>" % w)  # slab overflow -> re-plan
+    check_minimizer(engine, oracle, mixed, k, w, plan="k_minimizer_dense<%d> + ASCII side launch" % w)        # mixed: dense main launch + ASCII side launch
 
 
 def test_timed_entry_point_on_every_plan(engine):

@@ -318,6 +318,10 @@ def test_kmer_codes(engine, oracle, k, canonical, circular):
              "X" + rand_seq(rng, 60), rand_seq(rng, 60) + "-"]
     b = engine.batch(seqs)
     res = engine.run(b, engine.params(L.KMER, k, canonical=canonical, circular=circular))
+    # reads of up to 200 bases, some with letters beyond ACGT: the stream kernel (mode 2: canonical codes, mode 3: both strands) with an ASCII
+    # side launch; the two-strand mode of a circular call has no stream kernel and runs on the general ASCII kernel
+    want = "k_kmer<1>" if (circular and not canonical) else "k_nthash_fast<%d> + ASCII side launch" % (2 if canonical else 3)
+    assert res.plan()["kernel"] == want, (res.plan(), want)
     for i, q in enumerate(seqs):
         st, h, _ = res.read(i)
         try:
@@ -425,6 +429,11 @@ def test_simhash(engine, oracle, k, m, scale, canonical):
     seqs += ["GAACAATGTTCTCTAAAATTG", "GcACAATGTTCTCTAAAATTG", rand_seq(rng, 100, "ACGTN"), "A" * 100]
     b = engine.batch(seqs)
     res = engine.run(b, engine.params(L.SIMHASH, k, m=m, scale=scale, canonical=canonical))
+    nh = k - m + 1  # (one read carries an N: an ASCII side launch beside the bit-sliced kernel, the general ASCII kernel for the whole batch otherwise)
+    if nh <= 63:
+        assert res.plan()["kernel"].startswith("k_simhash_fast<%d," % (5 if nh <= 31 else 6)) and res.plan()["kernel"].endswith("> + ASCII side launch"), res.plan()
+    else:
+        assert res.plan()["kernel"] == "k_simhash<1>", res.plan()
     for i, q in enumerate(seqs):
         st, h, _ = res.read(i)
         try:

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from bio_amd import _lib as L
+from tests.plan_atlas import low_complexity
 
 pytestmark = pytest.mark.gpu
 
@@ -20,14 +21,6 @@ AA = "ACDEFGHIKLMNPQRSTVWY"
 
 def rand_seq(rng, n, alpha="ACGT"):
     return "".join(rng.choice(alpha) for _ in range(n))
-
-
-def low_complexity(rng, n):
-    """repeats and homopolymer runs: equal hashes inside a window, the case where an unstable buffer order could show"""
-    unit = rand_seq(rng, rng.randint(1, 6))
-    s = (unit * (n // len(unit) + 1))[:n]
-    cut = rng.randint(0, n)
-    return s[:cut] + rand_seq(rng, n - cut)
 
 
 # (k, w, lengths, kernel the planner must name) -- one row per kernel family of the minimizer path
@@ -42,10 +35,11 @@ CASES = [
     (15, 3, (260,), "k_minimizer_pkd"),             # four blocks per flush round
     (21, 13, (700,), "k_minimizer_pkd"),
     (31, 15, (150,), "k_minimizer_fast"),           # the reference's own benchmark parameters (sketch_test.go:128), w >= 14
-    (21, 5, (150,), "k_minimizer_"),               # dense selection (small w): unit rows or k_minimizer_dense
+    (21, 5, (150,), "k_minimizer_ring<5,false>"),   # dense selection (small w): unit rows
     (21, 11, (500, 700), "k_minimizer_pkd"),
     (15, 8, (5000, 9000), "over tiles"),                 # long sequences as tiles
-    (64, 20, (150, 220), "minimizer"),            # k = 64: the rotation's last step
+    (64, 20, (150, 220), "k_minimizer_fast<20,"),   # k = 64: the rotation's last step
+    (21, 16, (400,), "k_minimizer_fast<16,"),       # w >= 14, dense selection: k_minimizer_dense, which the poly-A read outgrows -- the re-plan's kernel
 ]
 
 
