@@ -811,7 +811,8 @@ extern "C" int bsk_sets_fetch_narrow(bsk_ctx *ctx, const bsk_sets *s, uint32_t *
 extern "C" int bsk_sets_fetch(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t count, uint64_t *offsets, uint64_t *values,
                               uint64_t value_cap) {
     if (!ctx || !s || !offsets) return fail_arg(ctx, "bsk_sets_fetch: null argument");
-    if (first + count > s->n_sets) return fail_arg(ctx, "bsk_sets_fetch: range outside the sets");
+    if (s->ctx != ctx) return fail_arg(ctx, "bsk_sets_fetch: the sets belong to another context");
+    if (first > s->n_sets || count > s->n_sets - first) return fail_arg(ctx, "bsk_sets_fetch: range outside the sets");  // (no wrap of first + count)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::vector<u64> o(count + 1);
     HIPCHK(ctx, hipMemcpy(o.data(), s->offsets + first, (count + 1) * 8, hipMemcpyDeviceToHost));

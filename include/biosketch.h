@@ -473,6 +473,9 @@ int bsk_result_sets_reuse(bsk_ctx *ctx, const bsk_result *r, int scope, int scal
  * (4 bytes per set + 8 per value over the link). */
 int bsk_sets_fetch_narrow(bsk_ctx *ctx, const bsk_sets *s, uint32_t *offsets, uint64_t *values, uint64_t value_cap);
 int bsk_sets_info(const bsk_sets *s, uint64_t *n_sets, uint64_t *n_values);
+/* Sets first .. first + count - 1 to the host: offsets[count + 1] rebased to 0, then their values (values may be NULL: offsets only).
+ * BSK_ERR_ARG for a range outside the sets, for more values than value_cap, and -- like bsk_sets_fetch_narrow -- for sets that belong to
+ * another context. */
 int bsk_sets_fetch(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t count, uint64_t *offsets, uint64_t *values,
                    uint64_t value_cap);
 int bsk_sets_device(const bsk_sets *s, const uint64_t **offsets, const uint64_t **values);
