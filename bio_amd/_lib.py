@@ -167,8 +167,13 @@ SYMBOLS = [
     ("bsk_pipeline_open_fastx_search", C.c_int, [C.POINTER(PipelineConfig), C.POINTER(C.c_char_p), C.c_int, C.POINTER(Params), C.POINTER(PipelineSearch), _pp]),
     ("bsk_pipeline_open_memory_search", C.c_int, [C.POINTER(PipelineConfig), _vp, _vp, C.c_uint64, C.c_int, C.POINTER(Params), C.POINTER(PipelineSearch), _pp]),
     ("bsk_chunk_hits", C.c_int, [C.POINTER(Chunk), _pp, _pp]),
+    ("bsk_sets_op", C.c_int, [_vp, _vp, _vp, C.c_int, _pp]),
+    ("bsk_sets_reduce", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, _pp]),
+    ("bsk_sets_plan", C.c_int, [_vp, C.POINTER(C.c_char_p), _u64p]),
 ]
 SETS_PER_SEQUENCE, SETS_WHOLE_BATCH = 0, 1
+SETOP_UNION, SETOP_INTERSECT, SETOP_DIFF, SETOP_SYMDIFF = 0, 1, 2, 3
+MEMBERS_ALL = 0xFFFFFFFF
 
 _lib = None
 

@@ -684,6 +684,8 @@ static int sets_impl(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bs
     res->ctx = ctx;
     res->n_sets = n_sets;
     res->n_values = 0;
+    res->plan[0] = 0;  // (a re-used object may have been a set operation's result: bsk_sets_plan describes those only)
+    res->by_path[0] = res->by_path[1] = res->by_path[2] = 0;
     SCHK(grow(&res->offsets, &res->c_offsets, (n_sets + 1) * 8));
     SCHK(grow(&res->values, &res->c_values, (N ? N : 1) * 8));
     if (N == 0) {
@@ -761,6 +763,10 @@ static int sets_impl(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bs
 
 hipError_t sets_sort_u64(void *tmp, size_t &tmp_bytes, u64 *in, u64 *out, size_t n, unsigned begin_bit, unsigned end_bit, hipStream_t st) {
     return rocprim::radix_sort_keys(tmp, tmp_bytes, in, out, n, begin_bit, end_bit, st);
+}
+
+hipError_t sets_sort_segments_u64(void *tmp, size_t &tmp_bytes, const u64 *in, u64 *out, u64 n, u64 n_segments, u64 *offs, hipStream_t st) {
+    return rocprim::segmented_radix_sort_keys(tmp, tmp_bytes, const_cast<u64 *>(in), out, (unsigned)n, (unsigned)n_segments, offs, offs + 1, 0, 64, st);
 }
 
 extern "C" int bsk_sets_info(const bsk_sets *s, uint64_t *n_sets, uint64_t *n_values) {

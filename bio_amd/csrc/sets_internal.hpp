@@ -13,11 +13,18 @@ struct bsk_sets {
     u64 *offsets = nullptr;  // [n_sets + 1]
     u64 *values = nullptr;   // [n_values] ascending inside a set
     size_t c_offsets = 0, c_values = 0;  // bytes allocated (grow-only when the object is re-used: bsk_result_sets_reuse)
+    char plan[256] = "";     // setops.hip: what the last bsk_sets_op / bsk_sets_reduce into this object ran (bsk_sets_plan)
+    u64 by_path[3] = {};     // ... and how many pairs of a bsk_sets_op took k_so_group, k_so_wave, k_so_tile
 };
 
 // rocprim::radix_sort_keys<u64> over bits [begin_bit, end_bit) on `st` (sets.hip: the instantiation its whole-batch sets use).
 // tmp == nullptr: *tmp_bytes receives the temporary storage it needs.
 hipError_t sets_sort_u64(void *tmp, size_t &tmp_bytes, u64 *in, u64 *out, size_t n, unsigned begin_bit, unsigned end_bit, hipStream_t st)
+    __attribute__((visibility("hidden")));
+
+// rocprim::segmented_radix_sort_keys<u64> over all 64 bits, segment g = [offs[g], offs[g + 1]) (sets.hip: the instantiation its
+// per-sequence sets use; `in` is only read).  tmp == nullptr: *tmp_bytes receives the temporary storage it needs.
+hipError_t sets_sort_segments_u64(void *tmp, size_t &tmp_bytes, const u64 *in, u64 *out, u64 n, u64 n_segments, u64 *offs, hipStream_t st)
     __attribute__((visibility("hidden")));
 
 namespace {

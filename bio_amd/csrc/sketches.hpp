@@ -186,6 +186,27 @@ class DeviceSets : public Owned<bsk_sets, bsk_sets_release> {
         bsk_sets_info(p_, &n, nullptr);
         return n;
     }
+    int fetch(Engine &e, std::vector<uint64_t> &offsets, std::vector<uint64_t> &values) const {
+        uint64_t n = 0, nv = 0;
+        int rc = bsk_sets_info(p_, &n, &nv);
+        if (rc != BSK_OK) return rc;
+        offsets.assign(n + 1, 0);
+        values.assign(nv + 1, 0);
+        rc = bsk_sets_fetch(e.ctx(), p_, 0, n, offsets.data(), values.data(), nv + 1);
+        values.resize(nv);
+        return rc;
+    }
+    // set algebra (bsk_sets_op / bsk_sets_reduce) INTO this object: empty, or the result of an earlier op / reduce on this engine (its
+    // device arrays are kept and only grow); it must be neither a nor b.  which: BSK_SETOP_*; a b of one set is combined with every set of a
+    int op(Engine &e, const DeviceSets &a, const DeviceSets &b, int which) { return bsk_sets_op(e.ctx(), a.get(), b.get(), which, &p_); }
+    // group g: sets group_offsets[g] .. group_offsets[g + 1] - 1 of s; the values at least min_members of them hold (1: union,
+    // BSK_MEMBERS_ALL: intersection)
+    int reduce(Engine &e, const DeviceSets &s, const std::vector<uint64_t> &group_offsets, uint32_t min_members = 1) {
+        if (group_offsets.empty()) return BSK_ERR_ARG;
+        return bsk_sets_reduce(e.ctx(), s.get(), group_offsets.data(), group_offsets.size() - 1, min_members, &p_);
+    }
+    // pairs of the last op into this object that took the group, wave and tiled path
+    void paths(uint64_t n_by_path[3]) const { bsk_sets_plan(p_, nullptr, n_by_path); }
 };
 
 // hits of a search (bsk_hits): CSR by query, target ids ascending inside a query

@@ -288,6 +288,50 @@ class Sets:
         self.eng._chk(self.eng.lib.bsk_index_build(self.eng.ctx, self.h, C.byref(h)))
         return Index(self.eng, h, np.diff(self.offsets()))
 
+    # -- set algebra (bsk_sets_op / bsk_sets_reduce): the result is a Sets of the same engine, left on the device
+    def _into(self, into: Optional["Sets"], call) -> "Sets":
+        h = into.h if into is not None and into.h else C.c_void_p()
+        rc = call(C.byref(h))
+        if into is not None:
+            into.h = h if h.value else None  # (kept on an argument error, released by the library on any other)
+        self.eng._chk(rc)
+        if into is None:
+            into = Sets(self.eng, h)
+        return into
+
+    def op(self, other: "Sets", op: int, into: Optional["Sets"] = None) -> "Sets":
+        """Set i of the result is self[i] op other[i]; an `other` of exactly one set is combined with every set of self (bsk_sets_op).
+        into: the Sets of an earlier operation on this engine, whose device arrays are kept and only grow."""
+        return self._into(into, lambda out: self.eng.lib.bsk_sets_op(self.eng.ctx, self.h, other.h, op, out))
+
+    def union(self, other: "Sets", into: Optional["Sets"] = None) -> "Sets":
+        return self.op(other, L.SETOP_UNION, into)
+
+    def intersect(self, other: "Sets", into: Optional["Sets"] = None) -> "Sets":
+        return self.op(other, L.SETOP_INTERSECT, into)
+
+    def difference(self, other: "Sets", into: Optional["Sets"] = None) -> "Sets":
+        """self[i] minus other[i]"""
+        return self.op(other, L.SETOP_DIFF, into)
+
+    def symmetric_difference(self, other: "Sets", into: Optional["Sets"] = None) -> "Sets":
+        return self.op(other, L.SETOP_SYMDIFF, into)
+
+    def reduce(self, group_offsets, min_members: int = 1, into: Optional["Sets"] = None) -> "Sets":
+        """One set per run of consecutive sets (group g: sets group_offsets[g] .. group_offsets[g + 1] - 1): the values at least
+        min_members of the run's sets hold -- 1: their union, L.MEMBERS_ALL: their intersection (bsk_sets_reduce)."""
+        go = np.ascontiguousarray(group_offsets, np.uint64)
+        if go.ndim != 1 or go.size == 0:
+            raise ValueError("group_offsets: a one-dimensional array of n_groups + 1 entries")
+        return self._into(into, lambda out: self.eng.lib.bsk_sets_reduce(self.eng.ctx, self.h, go.ctypes.data, go.size - 1, min_members, out))
+
+    def plan(self):
+        """What made these sets (bsk_sets_plan): a description and the pairs of the last op() that took the group, wave and tiled
+        path; sets of any other origin report an empty string and zeros."""
+        p, n = C.c_char_p(), (C.c_uint64 * 3)()
+        self.eng._chk(self.eng.lib.bsk_sets_plan(self.h, C.byref(p), n))
+        return dict(plan=(p.value or b"").decode(), n_by_path=[int(n[0]), int(n[1]), int(n[2])])
+
     def close(self):
         if self.h:
             self.eng.lib.bsk_sets_release(self.h)

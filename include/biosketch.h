@@ -481,6 +481,33 @@ int bsk_sets_fetch(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t cou
 int bsk_sets_device(const bsk_sets *s, const uint64_t **offsets, const uint64_t **values);
 void bsk_sets_release(bsk_sets *s);
 
+/* ---- set algebra on sketch sets ----------------------------------------------------
+ * bsk_sets_op: out[i] = a[i] op b[i] when b holds as many sets as a; when b holds exactly one set (and a any other number) every
+ * set of a is combined with that one set (broadcast: masking a host set out of every read set).  Anything else is BSK_ERR_ARG, as
+ * is an unknown op.  The output has a's number of sets, strictly ascending inside a set, and is an ordinary bsk_sets of ctx:
+ * index it, search it, fetch it.  a == b (the same object) is legal.  *out: NULL, or the object of an earlier bsk_sets_op /
+ * bsk_sets_reduce on this context, whose device arrays are kept and only grow; *out == a or *out == b is BSK_ERR_ARG.  Error rules
+ * as bsk_index_search: an argument error leaves *out as it was, any other error releases it and sets *out to NULL.  a and b must
+ * belong to ctx.  Inputs that hold 2^32 values or more together are BSK_ERR_UNSUPPORTED.  Any u64 is a legal value, 0 and 2^64-1
+ * included.  A merge, not a sort: pairs of few values take a group of 16 lanes, larger ones a wavefront, and beyond one
+ * wavefront's LDS the merged sequence is cut into tiles that spread over the device (bsk_sets_plan counts the pairs per path). */
+enum { BSK_SETOP_UNION = 0, BSK_SETOP_INTERSECT = 1, BSK_SETOP_DIFF = 2 /* a \ b */, BSK_SETOP_SYMDIFF = 3 };
+int bsk_sets_op(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, int op, bsk_sets **out);
+
+/* bsk_sets_reduce: the groups are runs of consecutive sets of s -- group g is sets group_offsets[g] .. group_offsets[g + 1] - 1;
+ * group_offsets[0] == 0, non-decreasing, group_offsets[n_groups] == the number of sets of s, else BSK_ERR_ARG (checked on the
+ * host, nothing kept).  Output set g holds the values that occur in at least min_members of the group's member sets: 1 is the
+ * union, BSK_MEMBERS_ALL the intersection over every member (empty members included: one empties it), any other m keeps the
+ * values of >= m members (a group of fewer members yields the empty set); 0 is BSK_ERR_ARG.  An empty group yields an empty set.
+ * *out as in bsk_sets_op; *out == s is BSK_ERR_ARG.  The host pointer is not retained. */
+#define BSK_MEMBERS_ALL 0xFFFFFFFFu
+int bsk_sets_reduce(bsk_ctx *ctx, const bsk_sets *s, const uint64_t *group_offsets /* host, [n_groups+1] */,
+                    uint64_t n_groups, uint32_t min_members, bsk_sets **out);
+
+/* what made these sets: a short description, and how many pairs of the last bsk_sets_op into s took the group, wave and tiled
+ * path; sets made by any other call report an empty string and zeros */
+int bsk_sets_plan(const bsk_sets *s, const char **plan, uint64_t n_by_path[3]);  /* either out-pointer may be NULL */
+
 /* ---- containment search of sets against a device-resident index ----------------------------------------------------
  * What a kmcp-style consumer does with the sets: for every query set (a read, a genome), which target sets share how many values
  * with it -- containment shared / |q|, Jaccard shared / (|q| + |t| - shared) -- computed where the sets already are.
