@@ -18,9 +18,20 @@
 //     reads with real 64-bit ties (a k-mer and its reverse complement in one window, homopolymers) always -- is appended to a list
 //     and run afterwards by the exact 64-bit machine (k_minimizer_dense<W, true>), which also evaluates BSK_ST_FIRST_WINDOW_TIE;
 //     everywhere else no tie exists and the flag is 0.
+//     The suffix pass leaves slot 0 out (S[0] is never read: step o of the next block reads S[o + 1] and then overwrites S[o]), and with
+//     it the check S[0] ^ S[1].  Nothing is lost: a key tie of the block's first element a_0 with a later a_j can only matter in a
+//     window that contains a_0, every such window ends inside the same block, and there the pair meets as prefix minimum against new
+//     element at step j, with key(P_{j-1}) = key(a_0) -- the first of the three checks.
+//   * the block loop (PkMin::run) is two loops: block PAIRS while another block follows the pair and every lane with a read fills both
+//     -- no per-lane window test, both suffix passes unconditional, one scalar compare and branch per pair --, then the ragged variants
+//     for what is left (at least one block; in a fixed-length unit at most two).  The loops carry twice the number of the base that
+//     enters and of the one that leaves at slot 0 as two opaque scalars (bits 5.. index the packed word, bits 0..4 are v_alignbit's
+//     shift): two s_add per block where the compiler re-derived six values from i0.
 // LDS layout: paired columns (lanes l and l + 32 fill one column from both ends) and 16-bit positions as in k_minimizer_fast, 58 rows,
-// eight waves per CU (PkLds); the copy-out is pk_copyout below.  The kernel is bound by what two waves per SIMD issue in order: what
-// pays is removing instructions of any kind, not cheaper encodings (profiles/NOTEBOOK.md, round 3).
+// eight waves per CU (PkLds); the copy-out is pk_copyout below.  The kernel is bound by what two waves per SIMD issue in order: cheaper
+// encodings buy nothing, removing VALU instructions pays about in proportion (profiles/NOTEBOOK.md, rounds 3 and 7), removing scalar
+// instructions, waits and branches pays far less than their count (round 8: -4 % of a block's instructions, none of them VALU steps,
+// for -1.5 % of the time), and a wait saved by waiting longer costs time.
 // (Tried first: byte positions + the copy-out's tables laid over the hash tables = 17.7 KB, nine waves per CU under a 168-VGPR cap.
 // The ninth wave was worth 3-4.7 %; the cap cost spills, the byte positions a wrap rule in the copy-out and a read-length limit.)
 #pragma once
@@ -45,7 +56,7 @@ __device__ __forceinline__ void pk_unroll(F &&f) {
 // reads select 58 tuples together -- 0.8 % of the units at k=21 w=11, 150 bp, against 4.1 % with 56 rows (measured: the tail is
 // heavier than normal), and both reads of such a column go to the exact machine afterwards.  The room comes from laying the copy-out's tables
 // (head words, owner table) over the two hash-phase tables, which a wavefront keeps in four VGPRs and writes back at the start of
-// every unit (PkTabs).  20 248 B: still eight waves per CU.
+// every unit (PkTabs).  20 240 B: still eight waves per CU.
 #ifndef BSK_PK_ROWS
 #define BSK_PK_ROWS 58
 #endif
@@ -174,7 +185,7 @@ struct PkMin {
     // carry-in) and stored as it is; pk_copyout<.., true> turns it into strand << 31 | position with one v_alignbit.  RINGM keeps
     // strand << 15 | position (flush_groups and flush_last read it), SELM stages nothing.
     static constexpr bool POS2 = !RINGM && !SELM;
-    u32 i2;  // POS2: 2 * i0 of the block being hashed, in a VGPR
+    u32 i2;  // POS2: 2 * i0 of the odd block of the pair being hashed (run() advances it once per pair), in a VGPR
 
     __device__ __forceinline__ void set_words(const PkWords &p) {
         wr = (u32x16){p.a.x, p.a.y, p.a.z, p.a.w, p.b.x, p.b.y, p.b.z, p.b.w, p.c.x, p.c.y, p.c.z, p.c.w, p.d.x, p.d.y, p.d.z, p.d.w};
@@ -285,24 +296,40 @@ struct PkMin {
     //        without a read)
     // RAG:   windows end per lane (ragged batch, or the wave's last, partial block)
     // PAR:   parity of the block: its slots are idx PAR*16 + o, the previous block's (1-PAR)*16 + o
-    // SUFFIX: another block follows (the suffix minima are needed)
+    // suffix: another block follows (the suffix minima are needed)
+    // One whole block from i0 alone, for callers with a block loop of their own: k_minimizer_pkd (RINGM, kernels_pkd.hpp).  run() below
+    // calls steps(), suffix_pass() and tail() itself.
     template <bool FIRST, bool RAG, int PAR>
     __device__ __forceinline__ void block(u32 i0, u32 okbit, bool suffix) {
+        static_assert(!POS2, "POS2 (k_minimizer_pk): i2 is advanced by run()");
+        const u32 t0 = i0 + (u32)k - 1, p0 = FIRST ? 0u : i0 - 1u;
+        steps<FIRST, RAG, PAR>(2u * t0, 2u * p0, i0, okbit);
+        if (suffix) suffix_pass();
+        tail<FIRST, PAR>(i0);
+    }
+
+    // The W steps of a block.  t2 / p2: twice the number of the base that enters / leaves at slot 0 (wave-uniform) -- bits 5.. are the
+    // index of its packed word, bits 0..4 the shift of v_alignbit, so run() carries the two and advances them by 2 W: two s_add per
+    // block where deriving both pairs from i0 took six.  i0 itself is read by the ragged variants, RINGM and SELM only.
+    // POS2: i2 is twice the first k-mer of the block PAIR (run() advances it once per odd block); an even block adds 2 W to its
+    // inline slot constants instead.
+    template <bool FIRST, bool RAG, int PAR>
+    __device__ __forceinline__ void steps(u32 t2, u32 p2, u32 i0, u32 okbit) {
         constexpr int CB = PAR * 16, PB = (1 - PAR) * 16;
         constexpr int XC = PkCfg<W>::XC;
-        const u32 t0 = i0 + (u32)k - 1, p0 = FIRST ? 0u : i0 - 1u;
+        constexpr int O2 = PAR ? 0 : 2 * W;
         u32 in_lo, in_hi, out_lo, out_hi;
         if constexpr (RINGM) {  // requested a block ago; the next block's go out now
             in_lo = this->in_lo, in_hi = this->in_hi, out_lo = this->out_lo, out_hi = this->out_hi;
             load_block_words(i0 + (u32)W);
         } else {
-            word2(t0 >> 4, in_lo, in_hi);
-            word2(p0 >> 4, out_lo, out_hi);
+            word2(t2 >> 5, in_lo, in_hi);
+            word2(p2 >> 5, out_lo, out_hi);
         }
-        const u32 cinb = __builtin_amdgcn_alignbit(in_hi, in_lo, (t0 & 15) * 2);  // code of slot o at bits [2o, 2o+2)
+        const u32 cinb = __builtin_amdgcn_alignbit(in_hi, in_lo, t2 & 31u);  // code of slot o at bits [2o, 2o+2)
         u32 coutb;
         if (FIRST) coutb = out_lo << 2;  // slot 0: nothing leaves; slot o >= 1 sees base o-1
-        else coutb = __builtin_amdgcn_alignbit(out_hi, out_lo, (p0 & 15) * 2);
+        else coutb = __builtin_amdgcn_alignbit(out_hi, out_lo, p2 & 31u);
         // table offsets: nibble j of E / O = (out << 2 | in) of slot 2j / 2j+1, so a slot's row offset is (word >> n) & 0xF0
         const u32 E = (cinb & 0x33333333u) | ((coutb & 0x33333333u) << 2);
         const u32 O = ((cinb >> 2) & 0x33333333u) | (coutb & 0xCCCCCCCCu);
@@ -332,11 +359,8 @@ struct PkMin {
         };
         fetch(0);
         if (XC < W) fetch(XC);
-        const u32 pbase = (u32)__builtin_amdgcn_readfirstlane((int)(i0 - (u32)W));
-        if constexpr (POS2) {
-            i2 = 2u * i0;
-            asm volatile("" : "+v"(i2));  // (one v_mov per block into a VGPR: with the carry-in the v_addc reads its one SGPR already)
-        }
+        u32 pbase = 0;
+        if constexpr (!POS2) pbase = (u32)__builtin_amdgcn_readfirstlane((int)(i0 - (u32)W));
         if (!FIRST) guard();
         u32 vb = 0;
         if (RAG && !FIRST) {  // bit o: the window ending at slot o exists for this lane
@@ -358,7 +382,7 @@ struct PkMin {
                 // 2 * (i0 + o) + strand in one v_addc_co_u32: 2o (inline constant) + 2 i0 (a VGPR) + the strand mask as carry-in.  (The VOP3
                 // form, carry-in from the compare's SGPR pair: a VOP2 reading VCC would need two wait states behind the compare.)
                 lmask co;
-                asm("v_addc_co_u32_e64 %0, %1, %2, %3, %4" : "=v"(SB[o]), "=s"(co) : "n"(2 * o), "v"(i2), "s"(rev));
+                asm("v_addc_co_u32_e64 %0, %1, %2, %3, %4" : "=v"(SB[o]), "=s"(co) : "n"(O2 + 2 * o), "v"(i2), "s"(rev));
             } else {
                 asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(SB[o]) : "v"(c8000), "s"(rev));  // strand << 15 in one select (0x8000 kept in a VGPR: VOP3 takes no literal)
             }
@@ -390,16 +414,25 @@ struct PkMin {
             }
             S[o] = pk;
         });
-        if (suffix) {
+    }
+
+    // Suffix minima of the block just hashed, for the block that follows it.  Slot 0 is left out: step o of the next block reads
+    // S[o + 1] and then overwrites S[o], so S[0] is never read, and its tie check is covered by the prefix checks (header comment).
+    __device__ __forceinline__ void suffix_pass() {
 #pragma unroll
-            for (int q = W - 2; q >= 0; --q) {
+        for (int q = W - 2; q >= 1; --q) {
 #ifndef PK_NOTIE
-                const u32 d = S[q] ^ S[q + 1];
-                tmin = tmin < d ? tmin : d;
+            const u32 d = S[q] ^ S[q + 1];
+            tmin = tmin < d ? tmin : d;
 #endif
-                S[q] = S[q] < S[q + 1] ? S[q] : S[q + 1];
-            }
+            S[q] = S[q] < S[q + 1] ? S[q] : S[q + 1];
         }
+    }
+
+    // after the steps of block i0: the previous block's slots are all emitted
+    template <bool FIRST, int PAR>
+    __device__ __forceinline__ void tail(u32 i0) {
+        constexpr int PB = (1 - PAR) * 16;
         if constexpr (SELM) {
             if (!FIRST) {  // the previous block (number i0 / W - 1) is final: its word leaves
                 const u32 wsel = (bm >> PB) & ((1u << W) - 1u);
@@ -407,7 +440,8 @@ struct PkMin {
                 nsel += (u32)__builtin_popcount(wsel);
             }
         }
-        if (!FIRST) bm &= PAR ? 0xffff0000u : 0x0000ffffu;  // the previous block's slots are all emitted
+        // the previous block's slots are all emitted.  (VOP2 with a literal: left to the compiler the mask goes through an s_mov into a v_bitop3)
+        if (!FIRST) asm("v_and_b32_e32 %0, %1, %0" : "+v"(bm) : "n"(PAR ? 0xffff0000u : 0x0000ffffu));
     }
 
     // the last block's own slots
@@ -471,32 +505,67 @@ struct PkMin {
         }
     }
 
-    // nk_min: the fewest windows of a lane WITH a read (fixed-length batches: nk_max): the blocks every such lane fills need no per-lane
-    // window test -- in a length-binned unit that is all but the last block or two (round 5; until then ragged batches took the test in every block)
+    // To the next block.  CARRY: t2 and p2 (steps()) advance on their own, opaque to the compiler, and i0 follows p2 -- where nothing
+    // reads it (the steady blocks of k_minimizer_pk) it costs nothing.  SELM reads i0 in every block, for its row of selection words:
+    // there the carried scalars only add to it (and spill at W = 4, 8), so its three values stay the compiler's to derive.
+    static constexpr bool CARRY = !SELM;
+    __device__ __forceinline__ void advance(u32 &i0, u32 &t2, u32 &p2) const {
+        if constexpr (CARRY) {
+            t2 += 2u * W, p2 += 2u * W;
+            asm volatile("" : "+s"(t2), "+s"(p2));
+            i0 = (p2 >> 1) + 1u;
+        } else {
+            i0 += W;
+            t2 = 2u * (i0 + (u32)k - 1u), p2 = 2u * (i0 - 1u);
+        }
+    }
+
+    // nk_min: the fewest windows of a lane WITH a read (fixed-length batches: nk_max).
+    // Two loops.  The steady loop runs block PAIRS (odd, even) while a further block follows the pair and every lane with a read fills
+    // both (i0 + 2 W < nk_min): no per-lane window test, both suffix passes unconditional, ONE scalar compare and branch per pair.
+    // What is left -- at least one block, in a fixed-length unit at most two -- runs in the ragged variants (a full block's window
+    // mask is all ones there), a compare per block for "another block follows".  The loops carry t2 / p2 (steps()) as opaque scalars:
+    // left to itself the compiler keeps i0 and 2 i0 and re-derives six values per block from them.
     __device__ __forceinline__ void run(u32 nk_max, bool ok, u32 nk_min, u32 slot0, int step, u32 col8) {
         begin(slot0, step, col8);
-        block<true, false, 0>(0, ok ? 1u : 0u, nk_max > (u32)W);
+        if constexpr (POS2) i2 = (u32)(-2 * W);  // (block 0 is an even block: its slot constants start at 2 W)
+        steps<true, false, 0>(2u * ((u32)k - 1u), 0u, 0u, ok ? 1u : 0u);
+        if (nk_max <= (u32)W) {
+            drain<0>(0);
+            return;
+        }
+        suffix_pass();
         u32 i0 = W;
-        int last_par = 0;
-        for (;;) {
-            if (i0 >= nk_max) break;
-            // odd block
-            {
-                const bool more = i0 + W < nk_max;
-                if (i0 + W <= nk_min) block<false, false, 1>(i0, 1u, more);
-                else block<false, true, 1>(i0, 1u, more);
-            }
-            i0 += W;
+        u32 t2 = 2u * ((u32)W + (u32)k - 1u), p2 = 2u * ((u32)W - 1u);
+        if constexpr (CARRY) asm volatile("" : "+s"(t2), "+s"(p2));
+        // p2 < lim  <=>  i0 + 2 W < nk_min
+        const int lim = 2 * ((int)__builtin_amdgcn_readfirstlane((int)(nk_min < 0x8000u ? nk_min : 0x8000u)) - 2 * W - 1);
+        while ((int)p2 < lim) {
+            if constexpr (POS2) asm("v_add_u32_e32 %0, %1, %0" : "+v"(i2) : "n"(4 * W));
+            steps<false, false, 1>(t2, p2, i0, 1u);
+            suffix_pass();
+            tail<false, 1>(i0);
+            advance(i0, t2, p2);
+            steps<false, false, 0>(t2, p2, i0, 1u);
+            suffix_pass();
+            tail<false, 0>(i0);
+            advance(i0, t2, p2);
+        }
+        int last_par;
+        for (;;) {  // (i0 < nk_max here)
+            if constexpr (POS2) asm("v_add_u32_e32 %0, %1, %0" : "+v"(i2) : "n"(4 * W));
+            steps<false, true, 1>(t2, p2, i0, 1u);
+            tail<false, 1>(i0);
+            advance(i0, t2, p2);
             last_par = 1;
             if (i0 >= nk_max) break;
-            // even block
-            {
-                const bool more = i0 + W < nk_max;
-                if (i0 + W <= nk_min) block<false, false, 0>(i0, 1u, more);
-                else block<false, true, 0>(i0, 1u, more);
-            }
-            i0 += W;
+            suffix_pass();
+            steps<false, true, 0>(t2, p2, i0, 1u);
+            tail<false, 0>(i0);
+            advance(i0, t2, p2);
             last_par = 0;
+            if (i0 >= nk_max) break;
+            suffix_pass();
         }
         if (last_par) drain<1>(i0 - W);
         else drain<0>(i0 - W);
