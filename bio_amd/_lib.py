@@ -170,10 +170,18 @@ SYMBOLS = [
     ("bsk_sets_op", C.c_int, [_vp, _vp, _vp, C.c_int, _pp]),
     ("bsk_sets_reduce", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint32, _pp]),
     ("bsk_sets_plan", C.c_int, [_vp, C.POINTER(C.c_char_p), _u64p]),
+    ("bsk_result_sets_counted", C.c_int, [_vp, _vp, C.c_int, C.c_int, _pp]),
+    ("bsk_sets_counts_device", C.c_int, [_vp, _pp]),
+    ("bsk_sets_fetch_counts", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64]),
+    ("bsk_sets_from_host_counted", C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _pp]),
+    ("bsk_sets_op_counted", C.c_int, [_vp, _vp, _vp, C.c_int, _pp]),
+    ("bsk_sets_filter_counts", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _pp]),
+    ("bsk_sets_totals", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp]),
 ]
 SETS_PER_SEQUENCE, SETS_WHOLE_BATCH = 0, 1
 SETOP_UNION, SETOP_INTERSECT, SETOP_DIFF, SETOP_SYMDIFF = 0, 1, 2, 3
 MEMBERS_ALL = 0xFFFFFFFF
+COUNTOP_ADD, COUNTOP_KEEP, COUNTOP_DROP = 0, 1, 2
 
 _lib = None
 

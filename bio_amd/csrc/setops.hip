@@ -60,15 +60,34 @@ struct SoSpan {
     }
     __device__ __forceinline__ u64 t(u64 p) const { return (ao[p + 1] - ao[p]) + (bo[p * bstep + 1] - bo[p * bstep]); }
 };
+// bsk_sets_op_counted's pairs: a second step factor (astep 0: a's only set against every set of b -- one sample against every genome)
+struct SoSpanAB {
+    const u64 *ao, *bo;
+    u64 astep, bstep;
+    __device__ __forceinline__ void get(u64 p, u64 &a0, u32 &na, u64 &b0, u32 &nb) const {
+        a0 = ao[p * astep];
+        na = (u32)(ao[p * astep + 1] - a0);
+        b0 = bo[p * bstep];
+        nb = (u32)(bo[p * bstep + 1] - b0);
+    }
+    __device__ __forceinline__ u64 t(u64 p) const { return (ao[p * astep + 1] - ao[p * astep]) + (bo[p * bstep + 1] - bo[p * bstep]); }
+};
+// the counts that ride along in a counted write pass: an operand without counts (NULL) counts 1 for every value
+struct SoCounts {
+    const u32 *ca = nullptr, *cb = nullptr;
+    u32 *out = nullptr;
+};
+template <class SP>
 struct SoWaveOf {  // 1 for the pairs of k_so_wave
-    SoSpan s;
+    SP s;
     __device__ __forceinline__ u64 operator()(u64 p) const {
         const u64 t = s.t(p);
         return t > SO_GROUP_CAP && t <= SO_WAVE_CAP ? 1 : 0;
     }
 };
+template <class SP>
 struct SoTilesOf {  // tiles of a pair of k_so_tile (tiled: only whether it has any)
-    SoSpan s;
+    SP s;
     bool tiled;
     __device__ __forceinline__ u64 operator()(u64 p) const {
         const u64 t = s.t(p);
@@ -121,6 +140,19 @@ __device__ __forceinline__ bool so_rank(const u64 *A, u32 na, const u64 *B, u32 
     }
     return so_keep(op, from_a, matched);
 }
+// the same rule for the counted kernels, which also need to know whether the other set holds the value (the partner whose count ADD adds)
+__device__ __forceinline__ bool so_rank(const u64 *A, u32 na, const u64 *B, u32 nb, const SoEdge &e, u32 r, u32 i, int op, u64 &x, bool &from_a, bool &matched) {
+    const u32 j = r - i;
+    from_a = i < na && (j >= nb || A[i] <= B[j]);
+    if (from_a) {  // its copy in b, if any, is the first element of b that does not precede it: B[j], or the one behind the slice
+        x = A[i];
+        matched = j < nb ? B[j] == x : (e.has_next && e.b_next == x);
+    } else {  // its copy in a, if any, is the last element of a that precedes it: A[i - 1], or the one before the slice
+        x = B[j];
+        matched = i > 0 ? A[i - 1] == x : (e.has_prev && e.a_prev == x);
+    }
+    return so_keep(op, from_a, matched);
+}
 // LANES (16: a row of the wavefront, bits [shift, shift + 16) of a ballot; 64: all of it) take the merged ranks in order; tmax:
 // a bound of t that is the same in every lane of the wavefront.  Lane l's rank lies l ranks behind the first of its trip, whose
 // count of A's elements (i0) the trip before left behind: the merge-path search spans l + 1 candidates, log2(LANES) steps at most.
@@ -145,10 +177,55 @@ __device__ __forceinline__ u32 so_merge(const u64 *A, u32 na, const u64 *B, u32 
     }
     return base;
 }
+// The counted body (bsk_sets_op_counted): the same trips; in write mode the kept element's count goes to c.out beside its value.  c.ca /
+// c.cb point at the counts of A[0] / B[0] in global memory (NULL: every count is 1), c.out at the counts of dst[0].  An element of a that
+// b holds adds its partner's count under BSK_COUNTOP_ADD -- the partner so_rank matched it with, B[j], which for j == nb is the edge
+// element behind the b slice: cb[nb], read by index like any other.
+template <int LANES, bool WRITE>
+__device__ __forceinline__ u32 so_merge(const u64 *A, u32 na, const u64 *B, u32 nb, const SoEdge &e, int op, u32 tmax, int l, int shift, u64 *dst, SoCounts c) {
+    const u32 t = na + nb;
+    u32 base = 0, i0 = 0;
+    for (u32 r0 = 0; r0 < tmax; r0 += LANES) {
+        const u32 r = r0 + (u32)l;
+        u64 x = 0;
+        bool from_a = false, keep = false, matched = false;
+        u32 i = 0;
+        if (r < t) {
+            i = so_diag(A, na, B, nb, r, i0, (u32)l);
+            keep = so_rank(A, na, B, nb, e, r, i, op, x, from_a, matched);
+        }
+        u64 bits = __ballot(keep), abits = __ballot(from_a);
+        if (LANES == 16) {
+            bits = (bits >> shift) & 0xffffull;
+            abits = (abits >> shift) & 0xffffull;
+        }
+        if (WRITE && keep) {
+            const u32 slot = base + (u32)__builtin_popcountll(bits & ((1ull << l) - 1ull)), j = r - i;
+            dst[slot] = x;
+            u64 n;
+            if (from_a) {
+                n = c.ca ? c.ca[i] : 1u;
+                if (op == BSK_COUNTOP_ADD && matched) n += c.cb ? c.cb[j] : 1u;
+            } else {
+                n = c.cb ? c.cb[j] : 1u;
+            }
+            c.out[slot] = n > 0xffffffffull ? 0xffffffffu : (u32)n;  // ADD saturates
+        }
+        base += (u32)__builtin_popcountll(bits);
+        i0 += (u32)__builtin_popcountll(abits);
+    }
+    return base;
+}
+// the counts of a slice that starts a0 / b0 / o values into a's, b's and the output's arrays
+__device__ __forceinline__ SoCounts so_counts_at(SoCounts c, u64 a0, u64 b0, u64 o) {
+    return SoCounts{c.ca ? c.ca + a0 : nullptr, c.cb ? c.cb + b0 : nullptr, c.out ? c.out + o : nullptr};
+}
 
+// The three kernels take the counts as a trailing parameter PACK: bsk_sets_op launches them with an empty one -- the signatures, the
+// kernel arguments and the body (the first so_merge above) are those of the uncounted library --, bsk_sets_op_counted with one SoCounts.
 // ---- t <= SO_GROUP_CAP: a group of 16 lanes per pair ----
-template <bool WRITE>
-__global__ __launch_bounds__(256) void k_so_group(SoSpan sp, const u64 *av, const u64 *bv, u64 n, int op, u64 *cnt, const u64 *ooff, u64 *out) {
+template <bool WRITE, class SP = SoSpan, class... C>
+__global__ __launch_bounds__(256) void k_so_group(SP sp, const u64 *av, const u64 *bv, u64 n, int op, u64 *cnt, const u64 *ooff, u64 *out, C... sc) {
     __shared__ u64 lds[16][SO_GROUP_CAP];
     const int lane = threadIdx.x & 63, l = lane & 15, row = lane >> 4;
     const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((u64)gridDim.x * blockDim.x) >> 6;
@@ -165,16 +242,17 @@ __global__ __launch_bounds__(256) void k_so_group(SoSpan sp, const u64 *av, cons
         }
         for (u32 e = (u32)l; e < na + nb; e += 16) A[e] = e < na ? av[a0 + e] : bv[b0 + (e - na)];
         wave_sync_lds();
-        const u32 c = so_merge<16, WRITE>(A, na, A + na, nb, SoEdge{}, op, SO_GROUP_CAP, l, row * 16, WRITE && mine ? out + ooff[p] : nullptr);
+        const u32 c = so_merge<16, WRITE>(A, na, A + na, nb, SoEdge{}, op, SO_GROUP_CAP, l, row * 16, WRITE && mine ? out + ooff[p] : nullptr,
+                                          so_counts_at(sc, a0, b0, WRITE && mine ? ooff[p] : 0)...);
         if (!WRITE && mine && l == 0) cnt[p] = c;
         wave_sync_lds();
     }
 }
 
 // ---- t <= SO_WAVE_CAP: one wavefront per pair of the list ----
-template <bool WRITE>
-__global__ __launch_bounds__(64 * SO_WAVES) void k_so_wave(SoSpan sp, const u64 *av, const u64 *bv, const u32 *list, u64 nlist, int op, u64 *cnt, const u64 *ooff,
-                                                           u64 *out) {
+template <bool WRITE, class SP = SoSpan, class... C>
+__global__ __launch_bounds__(64 * SO_WAVES) void k_so_wave(SP sp, const u64 *av, const u64 *bv, const u32 *list, u64 nlist, int op, u64 *cnt, const u64 *ooff,
+                                                           u64 *out, C... sc) {
     __shared__ u64 lds[SO_WAVES][SO_WAVE_CAP];
     const int lane = threadIdx.x & 63;
     const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((u64)gridDim.x * blockDim.x) >> 6;
@@ -186,7 +264,7 @@ __global__ __launch_bounds__(64 * SO_WAVES) void k_so_wave(SoSpan sp, const u64 
         sp.get(p, a0, na, b0, nb);
         for (u32 e = (u32)lane; e < na + nb; e += 64) A[e] = e < na ? av[a0 + e] : bv[b0 + (e - na)];
         wave_sync_lds();
-        const u32 c = so_merge<64, WRITE>(A, na, A + na, nb, SoEdge{}, op, na + nb, lane, 0, WRITE ? out + ooff[p] : nullptr);
+        const u32 c = so_merge<64, WRITE>(A, na, A + na, nb, SoEdge{}, op, na + nb, lane, 0, WRITE ? out + ooff[p] : nullptr, so_counts_at(sc, a0, b0, WRITE ? ooff[p] : 0)...);
         if (!WRITE && lane == 0) cnt[p] = c;
         wave_sync_lds();
     }
@@ -198,7 +276,8 @@ __global__ __launch_bounds__(64 * SO_WAVES) void k_so_wave(SoSpan sp, const u64 
 // and where the tile starts in a_i (merge path along the tile's first diagonal; its start in b_i is the rest of the rank).  Twenty
 // dependent loads a tile -- hidden behind a million threads here, exposed in a kernel of twelve wavefronts per CU (the first version
 // searched inside k_so_tile, in both passes: 22.0 ms for P3 of DESIGN 3.7).
-__global__ void k_so_cuts(SoSpan sp, const u64 *av, const u64 *bv, const u64 *tfirst, u64 n, u64 ntiles, u32 *tpair, u32 *ta0) {
+template <class SP>
+__global__ void k_so_cuts(SP sp, const u64 *av, const u64 *bv, const u64 *tfirst, u64 n, u64 ntiles, u32 *tpair, u32 *ta0) {
     for (u64 tile = (u64)blockIdx.x * blockDim.x + threadIdx.x; tile < ntiles; tile += (u64)gridDim.x * blockDim.x) {
         u64 lo = 0, hi = n - 1;
         while (lo < hi) {
@@ -213,9 +292,9 @@ __global__ void k_so_cuts(SoSpan sp, const u64 *av, const u64 *bv, const u64 *tf
         ta0[tile] = so_diag(av + pa, na, bv + pb, nb, (u32)(tile - tfirst[lo]) * SO_TILE);
     }
 }
-template <bool WRITE>
-__global__ __launch_bounds__(64 * SO_WAVES) void k_so_tile(SoSpan sp, const u64 *av, const u64 *bv, const u64 *tfirst, const u32 *tpair, const u32 *ta0, u64 ntiles, int op,
-                                                           u64 *tcnt, const u64 *tpos, const u64 *ooff, u64 *out) {
+template <bool WRITE, class SP = SoSpan, class... C>
+__global__ __launch_bounds__(64 * SO_WAVES) void k_so_tile(SP sp, const u64 *av, const u64 *bv, const u64 *tfirst, const u32 *tpair, const u32 *ta0, u64 ntiles, int op,
+                                                           u64 *tcnt, const u64 *tpos, const u64 *ooff, u64 *out, C... sc) {
     __shared__ u64 lds[SO_WAVES][SO_TILE];
     const int lane = threadIdx.x & 63;
     const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((u64)gridDim.x * blockDim.x) >> 6;
@@ -236,13 +315,15 @@ __global__ __launch_bounds__(64 * SO_WAVES) void k_so_tile(SoSpan sp, const u64 
         const u32 sa = a1 - a0, sb = b1 - b0;  // sa + sb = r1 - r0 <= SO_TILE
         for (u32 i = (u32)lane; i < sa + sb; i += 64) A[i] = i < sa ? av[pa + a0 + i] : bv[pb + b0 + (i - sa)];
         wave_sync_lds();
-        const u32 c = so_merge<64, WRITE>(A, sa, A + sa, sb, e, op, sa + sb, lane, 0, WRITE ? out + ooff[p] + (tpos[tile] - tpos[t0]) : nullptr);
+        const u32 c = so_merge<64, WRITE>(A, sa, A + sa, sb, e, op, sa + sb, lane, 0, WRITE ? out + ooff[p] + (tpos[tile] - tpos[t0]) : nullptr,
+                                          so_counts_at(sc, pa + a0, pb + b0, WRITE ? ooff[p] + (tpos[tile] - tpos[t0]) : 0)...);
         if (!WRITE && lane == 0) tcnt[tile] = c;
         wave_sync_lds();
     }
 }
 
-__global__ void k_so_list(SoWaveOf f, const u64 *slot, u64 n, u32 *list) {
+template <class SP>
+__global__ void k_so_list(SoWaveOf<SP> f, const u64 *slot, u64 n, u32 *list) {
     for (u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (u64)gridDim.x * blockDim.x)
         if (f(p)) list[slot[p]] = (u32)p;
 }
@@ -328,21 +409,25 @@ hipError_t so_grow(u64 **p, size_t *cap, size_t bytes) {  // the result's own ar
 }
 u64 scan_parts(u64 n) { return (n + SCAN_CHUNK - 1) / SCAN_CHUNK + 2; }
 
-int op_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, int op, bsk_sets *res) {
+// SP = SoSpan, COUNTED = false: bsk_sets_op; SoSpanAB, true: bsk_sets_op_counted (the count pass is the same, the write pass also
+// writes res->counts)
+template <class SP, bool COUNTED>
+int op_impl(bsk_ctx *ctx, const SP sp, const u64 n, bool broadcast, const bsk_sets *a, const bsk_sets *b, int op, bsk_sets *res) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const u64 n = a->n_sets;
-    const SoSpan sp{a->offsets, b->offsets, b->n_sets == n ? 1ull : 0ull};
     res->n_sets = n;
     res->n_values = 0;
+    res->counted = false;
     res->plan[0] = 0;
     res->by_path[0] = res->by_path[1] = res->by_path[2] = 0;
     HIPCHK(ctx, so_grow(&res->offsets, &res->c_offsets, (n + 1) * 8));
     if (n == 0) {
         HIPCHK(ctx, so_grow(&res->values, &res->c_values, 8));
+        if (COUNTED) HIPCHK(ctx, sets_grow_counts(res, 1, true));
         HIPCHK(ctx, hipMemsetAsync(res->offsets, 0, 8, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
-        snprintf(res->plan, sizeof res->plan, "bsk_sets_op: no pairs");
+        res->counted = COUNTED;
+        snprintf(res->plan, sizeof res->plan, "%s: no pairs", COUNTED ? "bsk_sets_op_counted" : "bsk_sets_op");
         return BSK_OK;
     }
     Carve cp;
@@ -355,9 +440,9 @@ int op_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, int op, bsk_sets
     u32 *list = at<u32>(bp, o_list);
     HIPCHK(ctx, hipMemsetAsync(tot, 0, 64, st));  // [0] wave pairs, [1] tiles, [2] tiled pairs, [3] values of the tiles, [4] values
     // 1. the classes: the wave kernel's list, the tiled pairs' first tiles
-    HIPCHK(ctx, scan_counts(st, SoWaveOf{sp}, n, part, wslot, tot + 0, (u64 *)nullptr));
-    HIPCHK(ctx, scan_counts(st, SoTilesOf{sp, false}, n, part, tfirst, tot + 1, (u64 *)nullptr));
-    HIPCHK(ctx, scan_counts(st, SoTilesOf{sp, true}, n, part, tslot, tot + 2, (u64 *)nullptr));
+    HIPCHK(ctx, scan_counts(st, SoWaveOf<SP>{sp}, n, part, wslot, tot + 0, (u64 *)nullptr));
+    HIPCHK(ctx, scan_counts(st, SoTilesOf<SP>{sp, false}, n, part, tfirst, tot + 1, (u64 *)nullptr));
+    HIPCHK(ctx, scan_counts(st, SoTilesOf<SP>{sp, true}, n, part, tslot, tot + 2, (u64 *)nullptr));
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 24, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     const u64 NW = ctx->h_pinned[0], NT = ctx->h_pinned[1], NTP = ctx->h_pinned[2], NG = n - NW - NTP;
@@ -373,17 +458,17 @@ int op_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, int op, bsk_sets
         part2 = at<u64>(bt, o_part2);
         tpair = at<u32>(bt, o_tpair);
         ta0 = at<u32>(bt, o_ta0);
-        hipLaunchKernelGGL(k_so_cuts, dim3(so_grid(ctx, NT, 256, 16)), dim3(256), 0, st, sp, a->values, b->values, tfirst, n, NT, tpair, ta0);
+        hipLaunchKernelGGL(k_so_cuts<SP>, dim3(so_grid(ctx, NT, 256, 16)), dim3(256), 0, st, sp, a->values, b->values, tfirst, n, NT, tpair, ta0);
     }
-    if (NW) hipLaunchKernelGGL(k_so_list, dim3(so_grid(ctx, n, 256, 16)), dim3(256), 0, st, SoWaveOf{sp}, wslot, n, list);
+    if (NW) hipLaunchKernelGGL(k_so_list<SP>, dim3(so_grid(ctx, n, 256, 16)), dim3(256), 0, st, SoWaveOf<SP>{sp}, wslot, n, list);
     const unsigned g_group = so_grid(ctx, n, 16, SO_GROUP_BLOCKS_PER_CU), g_wave = so_grid(ctx, NW, SO_WAVES, SO_WAVE_BLOCKS_PER_CU),
                    g_tile = so_grid(ctx, NT, SO_WAVES, SO_TILE_BLOCKS_PER_CU);
     // 2. count pass
-    if (NG) hipLaunchKernelGGL(k_so_group<false>, dim3(g_group), dim3(256), 0, st, sp, a->values, b->values, n, op, cnt, (const u64 *)nullptr, (u64 *)nullptr);
+    if (NG) hipLaunchKernelGGL((k_so_group<false, SP>), dim3(g_group), dim3(256), 0, st, sp, a->values, b->values, n, op, cnt, (const u64 *)nullptr, (u64 *)nullptr);
     if (NW)
-        hipLaunchKernelGGL(k_so_wave<false>, dim3(g_wave), dim3(64 * SO_WAVES), 0, st, sp, a->values, b->values, list, NW, op, cnt, (const u64 *)nullptr, (u64 *)nullptr);
+        hipLaunchKernelGGL((k_so_wave<false, SP>), dim3(g_wave), dim3(64 * SO_WAVES), 0, st, sp, a->values, b->values, list, NW, op, cnt, (const u64 *)nullptr, (u64 *)nullptr);
     if (NT)
-        hipLaunchKernelGGL(k_so_tile<false>, dim3(g_tile), dim3(64 * SO_WAVES), 0, st, sp, a->values, b->values, tfirst, tpair, ta0, NT, op, tcnt, (const u64 *)nullptr,
+        hipLaunchKernelGGL((k_so_tile<false, SP>), dim3(g_tile), dim3(64 * SO_WAVES), 0, st, sp, a->values, b->values, tfirst, tpair, ta0, NT, op, tcnt, (const u64 *)nullptr,
                            (const u64 *)nullptr, (u64 *)nullptr);
     HIPCHK(ctx, hipGetLastError());
     // 3. the tiles' places inside their pairs, the pairs' places in the output
@@ -393,25 +478,33 @@ int op_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, int op, bsk_sets
     HIPCHK(ctx, hipStreamSynchronize(st));
     const u64 M = ctx->h_pinned[0];
     HIPCHK(ctx, so_grow(&res->values, &res->c_values, (M ? M : 1) * 8));
-    // 4. write pass: the same kernels, every kept value to its final place
-    if (M) {
-        if (NG) hipLaunchKernelGGL(k_so_group<true>, dim3(g_group), dim3(256), 0, st, sp, a->values, b->values, n, op, (u64 *)nullptr, res->offsets, res->values);
+    if (COUNTED) HIPCHK(ctx, sets_grow_counts(res, M ? M : 1, true));
+    // 4. write pass: the same kernels, every kept value to its final place (c: nothing, or the counts that ride along)
+    auto write = [&](auto... c) {
+        if (NG)
+            hipLaunchKernelGGL((k_so_group<true, SP, decltype(c)...>), dim3(g_group), dim3(256), 0, st, sp, a->values, b->values, n, op, (u64 *)nullptr, res->offsets, res->values, c...);
         if (NW)
-            hipLaunchKernelGGL(k_so_wave<true>, dim3(g_wave), dim3(64 * SO_WAVES), 0, st, sp, a->values, b->values, list, NW, op, (u64 *)nullptr, res->offsets,
-                               res->values);
+            hipLaunchKernelGGL((k_so_wave<true, SP, decltype(c)...>), dim3(g_wave), dim3(64 * SO_WAVES), 0, st, sp, a->values, b->values, list, NW, op, (u64 *)nullptr, res->offsets,
+                               res->values, c...);
         if (NT)
-            hipLaunchKernelGGL(k_so_tile<true>, dim3(g_tile), dim3(64 * SO_WAVES), 0, st, sp, a->values, b->values, tfirst, tpair, ta0, NT, op, (u64 *)nullptr, tpos, res->offsets,
-                               res->values);
+            hipLaunchKernelGGL((k_so_tile<true, SP, decltype(c)...>), dim3(g_tile), dim3(64 * SO_WAVES), 0, st, sp, a->values, b->values, tfirst, tpair, ta0, NT, op, (u64 *)nullptr, tpos,
+                               res->offsets, res->values, c...);
+    };
+    if (M) {
+        if constexpr (COUNTED) write(SoCounts{a->counted ? a->counts : nullptr, b->counted ? b->counts : nullptr, res->counts});
+        else write();
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, hipStreamSynchronize(st));
     res->n_values = M;
+    res->counted = COUNTED;
     res->by_path[0] = NG;
     res->by_path[1] = NW;
     res->by_path[2] = NTP;
     static const char *const names[4] = {"union", "intersect", "diff", "symdiff"};
-    snprintf(res->plan, sizeof res->plan, "bsk_sets_op %s%s: k_so_group (t <= %d) %llu pairs, k_so_wave (t <= %d) %llu, k_so_tile %llu pairs in %llu tiles of %d", names[op],
-             sp.bstep ? "" : " (broadcast)", SO_GROUP_CAP, (unsigned long long)NG, SO_WAVE_CAP, (unsigned long long)NW, (unsigned long long)NTP, (unsigned long long)NT,
+    static const char *const cnames[3] = {"add", "keep", "drop"};
+    snprintf(res->plan, sizeof res->plan, "%s %s%s: k_so_group (t <= %d) %llu pairs, k_so_wave (t <= %d) %llu, k_so_tile %llu pairs in %llu tiles of %d",
+             COUNTED ? "bsk_sets_op_counted" : "bsk_sets_op", COUNTED ? cnames[op] : names[op], broadcast ? " (broadcast)" : "", SO_GROUP_CAP, (unsigned long long)NG, SO_WAVE_CAP, (unsigned long long)NW, (unsigned long long)NTP, (unsigned long long)NT,
              SO_TILE);
     return BSK_OK;
 }
@@ -422,6 +515,7 @@ int reduce_impl(bsk_ctx *ctx, const bsk_sets *s, const uint64_t *group_offsets, 
     const u64 N = s->n_values;
     res->n_sets = G;
     res->n_values = 0;
+    res->counted = false;
     res->plan[0] = 0;
     res->by_path[0] = res->by_path[1] = res->by_path[2] = 0;
     HIPCHK(ctx, so_grow(&res->offsets, &res->c_offsets, (G + 1) * 8));
@@ -500,7 +594,28 @@ extern "C" int bsk_sets_op(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, i
         ctx->err = "bsk_sets_op: 2^32 sets or values or more (split the sets)";
         return BSK_ERR_UNSUPPORTED;
     }
-    return into(ctx, out, [&](bsk_sets *res) { return op_impl(ctx, a, b, op, res); });
+    const u64 n = a->n_sets;
+    const SoSpan sp{a->offsets, b->offsets, b->n_sets == n ? 1ull : 0ull};
+    return into(ctx, out, [&](bsk_sets *res) { return op_impl<SoSpan, false>(ctx, sp, n, sp.bstep == 0, a, b, op, res); });
+}
+
+// The counted algebra: BSK_COUNTOP_ADD / KEEP / DROP are union / intersection / difference on the values (the same numbers as
+// BSK_SETOP_*), the write pass also writes every kept value's count.  Pairing as bsk_sets_op, and besides: an a of exactly one set
+// against a b of n sets gives n sets, a op b[i].
+extern "C" int bsk_sets_op_counted(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, int op, bsk_sets **out) {
+    static_assert(BSK_COUNTOP_ADD == BSK_SETOP_UNION && BSK_COUNTOP_KEEP == BSK_SETOP_INTERSECT && BSK_COUNTOP_DROP == BSK_SETOP_DIFF, "so_keep takes the op as it is");
+    if (!ctx || !a || !b || !out) return fail_arg(ctx, "bsk_sets_op_counted: null argument");
+    if (a->ctx != ctx || b->ctx != ctx || (*out && (*out)->ctx != ctx)) return fail_arg(ctx, "bsk_sets_op_counted: the sets belong to another context");
+    if (*out == a || *out == b) return fail_arg(ctx, "bsk_sets_op_counted: *out is one of the inputs");
+    if (op != BSK_COUNTOP_ADD && op != BSK_COUNTOP_KEEP && op != BSK_COUNTOP_DROP) return fail_arg(ctx, "bsk_sets_op_counted: unknown op");
+    if (b->n_sets != a->n_sets && b->n_sets != 1 && a->n_sets != 1) return fail_arg(ctx, "bsk_sets_op_counted: a and b must hold as many sets, or one of them exactly one");
+    const u64 n = b->n_sets == a->n_sets || b->n_sets == 1 ? a->n_sets : b->n_sets;
+    if (n >= (1ULL << 32) || a->n_values + b->n_values >= (1ULL << 32)) {
+        ctx->err = "bsk_sets_op_counted: 2^32 sets or values or more (split the sets)";
+        return BSK_ERR_UNSUPPORTED;
+    }
+    const SoSpanAB sp{a->offsets, b->offsets, a->n_sets == n ? 1ull : 0ull, b->n_sets == n ? 1ull : 0ull};
+    return into(ctx, out, [&](bsk_sets *res) { return op_impl<SoSpanAB, true>(ctx, sp, n, sp.astep == 0 || sp.bstep == 0, a, b, op, res); });
 }
 
 extern "C" int bsk_sets_reduce(bsk_ctx *ctx, const bsk_sets *s, const uint64_t *group_offsets, uint64_t n_groups, uint32_t min_members, bsk_sets **out) {

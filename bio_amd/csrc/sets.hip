@@ -590,12 +590,12 @@ extern "C" void bsk_sets_release(bsk_sets *s) {
     if (s->ctx) (void)hipSetDevice(s->ctx->device);
     (void)hipFree(s->offsets);
     (void)hipFree(s->values);
+    (void)hipFree(s->counts);
     delete s;
 }
 
-static int sets_impl(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets *reuse, bsk_sets **out);
 extern "C" int bsk_result_sets(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets **out) {
-    return sets_impl(ctx, r, scope, scale, nullptr, out);
+    return sets_build(ctx, r, scope, scale, false, nullptr, out);
 }
 // The same into an EXISTING sets object (*sets may be NULL the first time): its device arrays are kept and only grow, so a streaming
 // caller -- one chunk after the other through one object per stream -- allocates nothing in steady state (hipMalloc / hipFree
@@ -606,12 +606,21 @@ extern "C" int bsk_result_sets_reuse(bsk_ctx *ctx, const bsk_result *r, int scop
     bsk_sets *old = *sets;
     if (old && old->ctx != ctx) return fail_arg(ctx, "bsk_result_sets_reuse: the sets belong to another context");
     *sets = nullptr;
-    return sets_impl(ctx, r, scope, scale, old, sets);
+    return sets_build(ctx, r, scope, scale, false, old, sets);
 }
-static int sets_impl(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets *reuse, bsk_sets **out) {
+// The same with every kept value's run length (bsk_sets::counts): how often the value occurred in its scope.  Counted calls always take
+// the general path -- the run lengths fall out of its sorted array, its flags and its scan (counts.hip: sets_run_counts).
+extern "C" int bsk_result_sets_counted(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets **sets) {
+    if (!sets) return fail_arg(ctx, "bsk_result_sets_counted: null argument");
+    bsk_sets *old = *sets;
+    if (old && old->ctx != ctx) return fail_arg(ctx, "bsk_result_sets_counted: the sets belong to another context");
+    *sets = nullptr;
+    return sets_build(ctx, r, scope, scale, true, old, sets);
+}
+int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool counted, bsk_sets *reuse, bsk_sets **out) {
     if (!ctx || !r || !out) {
         if (reuse) bsk_sets_release(reuse);
-        return fail_arg(ctx, "bsk_result_sets: null argument");
+        return fail_arg(ctx, counted ? "bsk_result_sets_counted: null argument" : "bsk_result_sets: null argument");
     }
     *out = nullptr;
     if (r->ctx != ctx || (scope != BSK_SETS_PER_SEQUENCE && scope != BSK_SETS_WHOLE_BATCH) || scale < 0) {
@@ -686,15 +695,18 @@ static int sets_impl(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bs
     res->n_values = 0;
     res->plan[0] = 0;  // (a re-used object may have been a set operation's result: bsk_sets_plan describes those only)
     res->by_path[0] = res->by_path[1] = res->by_path[2] = 0;
+    res->counted = false;  // (a re-used counted object keeps its counts array, not its counts)
     SCHK(grow(&res->offsets, &res->c_offsets, (n_sets + 1) * 8));
     SCHK(grow(&res->values, &res->c_values, (N ? N : 1) * 8));
     if (N == 0) {
         SCHK(hipMemsetAsync(res->offsets, 0, (n_sets + 1) * 8, st));
+        if (counted) SCHK(sets_grow_counts(res, 1, reuse != nullptr));
         SCHK(hipStreamSynchronize(st));
+        res->counted = counted;
         *out = res;
         return done(BSK_OK);
     }
-    if (scope == BSK_SETS_PER_SEQUENCE && max_count <= SMALL_CAP && !ctx->opt.sets_no_small) {
+    if (scope == BSK_SETS_PER_SEQUENCE && max_count <= SMALL_CAP && !ctx->opt.sets_no_small && !counted) {
         // short reads: one sequence per row of 16 lanes, bitonic network over DPP moves (k_sets_rows)
         u64 *ucount = nullptr, *dense = nullptr;
         SCHK(pool(2, N * 8, (void **)&dense));          // the sequences' distinct values at their input offsets
@@ -754,8 +766,15 @@ static int sets_impl(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bs
     hipLaunchKernelGGL(k_scatter_unique, dim3(grid_of(ctx, N, 256)), dim3(256), 0, st, vsorted, keep, pos, N, res->values);
     hipLaunchKernelGGL(k_new_offsets, dim3(grid_of(ctx, n_sets + 1, 256)), dim3(256), 0, st, set_offs, pos, n_sets, N, M, res->offsets);
     SCHK(hipGetLastError());
+    if (counted) {  // every kept head's run length: the sorted array, the flags and the positions are all still here
+        u64 *cpart = nullptr;
+        SCHK(sets_grow_counts(res, M ? M : 1, reuse != nullptr));
+        SCHK(pool(40, sets_run_counts_parts(N) * 8, (void **)&cpart));
+        SCHK(sets_run_counts(st, vsorted, keep, pos, N, maxhash, scale > 1, cpart, res->counts));
+    }
     SCHK(hipStreamSynchronize(st));
     res->n_values = M;
+    res->counted = counted;
 #undef SCHK
     *out = res;
     return done(BSK_OK);

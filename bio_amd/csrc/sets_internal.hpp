@@ -15,7 +15,23 @@ struct bsk_sets {
     size_t c_offsets = 0, c_values = 0;  // bytes allocated (grow-only when the object is re-used: bsk_result_sets_reuse)
     char plan[256] = "";     // setops.hip: what the last bsk_sets_op / bsk_sets_reduce into this object ran (bsk_sets_plan)
     u64 by_path[3] = {};     // ... and how many pairs of a bsk_sets_op took k_so_group, k_so_wave, k_so_tile
+    // counted sets (counts.hip): counts[i] = how often values[i] occurred.  `counted` says whether the array is valid: every entry
+    // that writes values into this object without counts clears it and keeps the array (grow-only, like the others).
+    u32 *counts = nullptr;   // [n_values]
+    size_t c_counts = 0;
+    bool counted = false;
 };
+
+// counts.hip: run lengths of the kept heads of a sorted, flagged array (what sets.hip's general path has after its scan).  keep[i] = 1
+// marks a kept head, pos[i] its place in the output; a run ends at the next kept head, at the first value above maxhash (filt) or at n.
+// part: sets_run_counts_parts(n) u64 of scratch.  All on `st`, nothing read back.
+u64 sets_run_counts_parts(u64 n) __attribute__((visibility("hidden")));
+hipError_t sets_run_counts(hipStream_t st, const u64 *v, const u32 *keep, const u64 *pos, u64 n, u64 maxhash, bool filt, u64 *part, u32 *counts)
+    __attribute__((visibility("hidden")));
+// the sets' counts array, grow-only (reuse: with slack)
+hipError_t sets_grow_counts(bsk_sets *s, u64 n, bool slack) __attribute__((visibility("hidden")));
+// bsk_result_sets / _reuse / _counted (sets.hip)
+int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool counted, bsk_sets *reuse, bsk_sets **out) __attribute__((visibility("hidden")));
 
 // rocprim::radix_sort_keys<u64> over bits [begin_bit, end_bit) on `st` (sets.hip: the instantiation its whole-batch sets use).
 // tmp == nullptr: *tmp_bytes receives the temporary storage it needs.

@@ -207,6 +207,41 @@ class DeviceSets : public Owned<bsk_sets, bsk_sets_release> {
     }
     // pairs of the last op into this object that took the group, wave and tiled path
     void paths(uint64_t n_by_path[3]) const { bsk_sets_plan(p_, nullptr, n_by_path); }
+
+    // ---- counted sets: values with their abundance (counts[i] belongs to values[i]) ----
+    // the counted sets of a result INTO this object (empty, or any sets of this engine: arrays kept, grow only)
+    int from_result_counted(Engine &e, const bsk_result *r, int scope, int scale = 1) { return bsk_result_sets_counted(e.ctx(), r, scope, scale, &p_); }
+    int from_host_counted(Engine &e, const std::vector<uint64_t> &offsets, const std::vector<uint64_t> &values, const std::vector<uint32_t> &counts) {
+        if (offsets.empty() || offsets.back() != values.size() || counts.size() != values.size()) return BSK_ERR_ARG;
+        bsk_sets_release(p_);
+        p_ = nullptr;
+        return bsk_sets_from_host_counted(e.ctx(), offsets.data(), offsets.size() - 1, values.empty() ? nullptr : values.data(), counts.empty() ? nullptr : counts.data(), &p_);
+    }
+    bool counted() const {
+        const uint32_t *c = nullptr;
+        return bsk_sets_counts_device(p_, &c) == BSK_OK && c != nullptr;
+    }
+    int fetch_counts(Engine &e, std::vector<uint32_t> &counts) const {
+        uint64_t n = 0, nv = 0;
+        int rc = bsk_sets_info(p_, &n, &nv);
+        if (rc != BSK_OK) return rc;
+        counts.assign(nv + 1, 0);
+        rc = bsk_sets_fetch_counts(e.ctx(), p_, 0, n, counts.data(), nv + 1);
+        counts.resize(nv);
+        return rc;
+    }
+    // which: BSK_COUNTOP_*; INTO this object as op(); an a of one set is combined with every set of b
+    int op_counted(Engine &e, const DeviceSets &a, const DeviceSets &b, int which) { return bsk_sets_op_counted(e.ctx(), a.get(), b.get(), which, &p_); }
+    int filter_counts(Engine &e, const DeviceSets &s, uint32_t min_count = 1, uint32_t max_count = 0xFFFFFFFFu) {
+        return bsk_sets_filter_counts(e.ctx(), s.get(), min_count, max_count, &p_);
+    }
+    int totals(Engine &e, std::vector<uint64_t> &out) const {
+        const uint64_t n = n_sets();
+        out.assign(n + 1, 0);
+        const int rc = bsk_sets_totals(e.ctx(), p_, 0, n, out.data());
+        out.resize(n);
+        return rc;
+    }
 };
 
 // hits of a search (bsk_hits): CSR by query, target ids ascending inside a query

@@ -212,6 +212,17 @@ class BatchResult:
                                                    C.byref(h)))
         return Sets(self.eng, h)
 
+    def counted_sets(self, whole_batch: bool = False, scale: int = 1, into: Optional["Sets"] = None) -> "Sets":
+        """device_sets() with every value's abundance (bsk_result_sets_counted): counts[i] = how many tuples of the set's scope hold
+        values[i].  into: a Sets of this engine to re-use (its device arrays are kept and only grow)."""
+        h = into.h if into is not None and into.h else C.c_void_p()
+        self.eng._opts()
+        rc = self.eng.lib.bsk_result_sets_counted(self.eng.ctx, self.h, L.SETS_WHOLE_BATCH if whole_batch else L.SETS_PER_SEQUENCE, scale, C.byref(h))
+        if into is not None:
+            into.h = h if h.value else None
+        self.eng._chk(rc)
+        return into if into is not None else Sets(self.eng, h)
+
     def compact(self):
         """bsk_result_compact: dense CSR copy left ON THE DEVICE -> (offsets_ptr, hash_ptr, pos_ptr or None, n_tuples); the arrays belong
         to the engine's context until its next compact()."""
@@ -324,6 +335,49 @@ class Sets:
         if go.ndim != 1 or go.size == 0:
             raise ValueError("group_offsets: a one-dimensional array of n_groups + 1 entries")
         return self._into(into, lambda out: self.eng.lib.bsk_sets_reduce(self.eng.ctx, self.h, go.ctypes.data, go.size - 1, min_members, out))
+
+    # -- counted sets (bsk_sets_*count*): values with their abundance
+    @property
+    def counted(self) -> bool:
+        """whether the sets carry counts (bsk_sets_counts_device gives an array)"""
+        p = C.c_void_p()
+        self.eng._chk(self.eng.lib.bsk_sets_counts_device(self.h, C.byref(p)))
+        return bool(p.value)
+
+    def fetch_counts(self) -> np.ndarray:
+        """bsk_sets_fetch_counts -> counts[n_values] (u32), parallel to fetch()'s values"""
+        inf = self.info()
+        c = np.zeros(max(inf["n_values"], 1), np.uint32)
+        self.eng._chk(self.eng.lib.bsk_sets_fetch_counts(self.eng.ctx, self.h, 0, inf["n_sets"], c.ctypes.data, c.size))
+        return c[: inf["n_values"]]
+
+    def op_counted(self, other: "Sets", op: int, into: Optional["Sets"] = None) -> "Sets":
+        """bsk_sets_op_counted: L.COUNTOP_ADD / KEEP / DROP; pairing as op(), and a self of one set is combined with every set of other"""
+        return self._into(into, lambda out: self.eng.lib.bsk_sets_op_counted(self.eng.ctx, self.h, other.h, op, out))
+
+    def add(self, other: "Sets", into: Optional["Sets"] = None) -> "Sets":
+        """the union's values, counts added (saturating at 2^32 - 1)"""
+        return self.op_counted(other, L.COUNTOP_ADD, into)
+
+    def keep(self, other: "Sets", into: Optional["Sets"] = None) -> "Sets":
+        """self's values that other holds, with self's counts"""
+        return self.op_counted(other, L.COUNTOP_KEEP, into)
+
+    def drop(self, other: "Sets", into: Optional["Sets"] = None) -> "Sets":
+        """self's values that other does not hold, with self's counts"""
+        return self.op_counted(other, L.COUNTOP_DROP, into)
+
+    def filter_counts(self, min_count: int = 1, max_count: Optional[int] = None, into: Optional["Sets"] = None) -> "Sets":
+        """the values with min_count <= count <= max_count (None: no upper bound) and their counts (bsk_sets_filter_counts)"""
+        hi = 0xFFFFFFFF if max_count is None else max_count
+        return self._into(into, lambda out: self.eng.lib.bsk_sets_filter_counts(self.eng.ctx, self.h, min_count, hi, out))
+
+    def totals(self) -> np.ndarray:
+        """per set the sum of its counts, u64 (bsk_sets_totals); the sets' sizes for sets without counts"""
+        ns = self.info()["n_sets"]
+        t = np.zeros(max(ns, 1), np.uint64)
+        self.eng._chk(self.eng.lib.bsk_sets_totals(self.eng.ctx, self.h, 0, ns, t.ctypes.data))
+        return t[:ns]
 
     def plan(self):
         """What made these sets (bsk_sets_plan): a description and the pairs of the last op() that took the group, wave and tiled
@@ -656,6 +710,18 @@ class Engine:
         h = C.c_void_p()
         self._chk(self.lib.bsk_sets_from_host(self.ctx, offsets.ctypes.data, len(offsets) - 1, values.ctypes.data if len(values) else None,
                                               C.byref(h)))
+        return Sets(self, h)
+
+    def sets_from_arrays_counted(self, offsets: np.ndarray, values: np.ndarray, counts: np.ndarray) -> Sets:
+        """sets_from_arrays with counts[len(values)] (u32, none of them 0): bsk_sets_from_host_counted"""
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        values = np.ascontiguousarray(values, np.uint64)
+        counts = np.ascontiguousarray(counts, np.uint32)
+        if offsets.ndim != 1 or len(offsets) < 1 or int(offsets[-1]) != len(values) or len(counts) != len(values):
+            raise ValueError("sets_from_arrays_counted: offsets must have n_sets + 1 entries and end at len(values) == len(counts)")
+        h = C.c_void_p()
+        self._chk(self.lib.bsk_sets_from_host_counted(self.ctx, offsets.ctypes.data, len(offsets) - 1, values.ctypes.data if len(values) else None,
+                                                      counts.ctypes.data if len(counts) else None, C.byref(h)))
         return Sets(self, h)
 
     def batch_from_packed(self, words: np.ndarray, desc: np.ndarray) -> Batch:

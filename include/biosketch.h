@@ -602,6 +602,34 @@ int bsk_pipeline_open_memory_search(const bsk_pipeline_config *cfg, const uint8_
 /* BSK_SINK_HITS chunks: offsets32 / offsets64 are the records' hit offsets, n_values the number of hits, hash == NULL */
 int bsk_chunk_hits(const bsk_chunk *c, const uint32_t **target, const uint32_t **shared);
 
+/* ---- counted sketch sets: abundance on the device ----------------------------------------------------
+ * A counted set is an ordinary bsk_sets plus a device array counts[n_values] (u32) parallel to values: how often the value occurred.
+ * Every other entry treats such an object as its values only; an entry that writes into a re-used counted object leaves it uncounted
+ * (the array is kept, like the others).
+ * bsk_result_sets_counted: scope, scale, the 2^32 limit and the *sets rules of bsk_result_sets_reuse (*sets may be NULL; arrays kept,
+ * grow only; on error the object is released and *sets is NULL); offsets and values are those of bsk_result_sets, counts[i] is the
+ * number of tuples of the set's scope -- the sequence, or the whole batch -- that hold values[i].  Values above MaxUint64 / scale are
+ * neither kept nor counted. */
+int bsk_result_sets_counted(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets **sets);
+int bsk_sets_counts_device(const bsk_sets *s, const uint32_t **counts);            /* *counts = NULL for an uncounted object */
+/* the counts of sets first .. first + count - 1 (range and cap rules of bsk_sets_fetch); BSK_ERR_ARG for an uncounted object */
+int bsk_sets_fetch_counts(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t count, uint32_t *counts, uint64_t count_cap);
+/* bsk_sets_from_host with counts[offsets[n_sets]]; a count of 0 is BSK_ERR_ARG (nothing is kept) */
+int bsk_sets_from_host_counted(bsk_ctx *ctx, const uint64_t *offsets, uint64_t n_sets, const uint64_t *values,
+                               const uint32_t *counts, bsk_sets **out);
+/* bsk_sets_op_counted: the values of ADD / KEEP / DROP are the union / intersection / difference of bsk_sets_op.  ADD: count
+ * ca + cb, saturating at 2^32 - 1; KEEP: the values of a that b holds, with a's counts; DROP: those b does not hold, with a's counts.
+ * An uncounted operand counts 1 for every value; the output is always counted.  Pairing as bsk_sets_op, and besides an a of exactly
+ * one set against a b of n sets yields n sets, a op b[i] (one sample against every genome).  *out, errors, a == b and the 2^32 limit
+ * as bsk_sets_op; bsk_sets_plan reports the pairs per path. */
+enum { BSK_COUNTOP_ADD = 0, BSK_COUNTOP_KEEP = 1, BSK_COUNTOP_DROP = 2 };
+int bsk_sets_op_counted(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, int op, bsk_sets **out);
+/* the values with min_count <= count <= max_count, and their counts; s must be counted; min_count == 0 or min_count > max_count is
+ * BSK_ERR_ARG; *out as in bsk_sets_reduce */
+int bsk_sets_filter_counts(bsk_ctx *ctx, const bsk_sets *s, uint32_t min_count, uint32_t max_count, bsk_sets **out);
+/* per set of the range the sum of its counts (u64: exact); an uncounted object gives the sets' sizes */
+int bsk_sets_totals(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t count, uint64_t *totals /* host */);
+
 #ifdef __cplusplus
 }
 #endif
