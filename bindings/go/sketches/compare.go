@@ -1,0 +1,130 @@
+//go:build biosketch
+
+package sketches
+
+/*
+#cgo LDFLAGS: -lbiosketch
+#include <stdlib.h>
+#include "biosketch.h"
+*/
+import "C"
+
+import (
+	"math"
+	"runtime"
+	"unsafe"
+)
+
+// ---- MinHash on the device: bottom-n sets and the dense all-pairs comparison ---------------------------------------------
+//
+// s.Bottom(1000, nil) is the Mash / sourmash num= sketch of every set; a.Compare(b, 1000, nil) walks, for every pair, the first
+// 1000 distinct values of the union and counts those both sets hold: Shared / Total is the Mash estimator of the Jaccard.
+// A limit of 0 walks the whole union: the exact Jaccard.
+
+// Bottom cuts every set to its min(n, size) smallest values, counts included for counted sets (bsk_sets_bottom).  into as in Op.
+func (s *Sets) Bottom(n uint64, into *Sets) (*Sets, error) {
+	if into == nil {
+		into = &Sets{eng: s.eng}
+		runtime.SetFinalizer(into, func(r *Sets) { C.bsk_sets_release(r.h) })
+	}
+	rc := C.bsk_sets_bottom(s.eng.ctx, s.h, C.uint64_t(n), &into.h)
+	runtime.KeepAlive(s)
+	return into, s.eng.err(rc)
+}
+
+// Compare is the result of (*Sets).Compare: two dense row-major matrices on the device, Shared and Total.
+type Compare struct {
+	eng *Engine
+	h   *C.bsk_compare
+}
+
+// Compare compares every set of a with every set of b (nil: of a itself) into `into` (nil the first time; the device arrays of an
+// earlier Compare are kept and only grow): bsk_sets_compare.
+func (a *Sets) Compare(b *Sets, limit uint64, into *Compare) (*Compare, error) {
+	if b == nil {
+		b = a
+	}
+	if into == nil {
+		into = &Compare{eng: a.eng}
+		runtime.SetFinalizer(into, func(m *Compare) { C.bsk_compare_release(m.h) })
+	}
+	rc := C.bsk_sets_compare(a.eng.ctx, a.h, b.h, C.uint64_t(limit), &into.h)
+	runtime.KeepAlive(a)
+	runtime.KeepAlive(b)
+	return into, a.eng.err(rc)
+}
+
+// Info returns the matrix's rows and columns and the limit it was computed with (bsk_compare_info).
+func (m *Compare) Info() (nA, nB, limit uint64) {
+	var a, b, l C.uint64_t
+	C.bsk_compare_info(m.h, &a, &b, &l)
+	runtime.KeepAlive(m)
+	return uint64(a), uint64(b), uint64(l)
+}
+
+// Plan describes what ran, and returns the tiles run, the rounds summed over them and the most rounds of one tile (bsk_compare_plan).
+func (m *Compare) Plan() (string, [3]uint64) {
+	var p *C.char
+	var f [3]C.uint64_t
+	C.bsk_compare_plan(m.h, &p, &f[0])
+	runtime.KeepAlive(m)
+	return C.GoString(p), [3]uint64{uint64(f[0]), uint64(f[1]), uint64(f[2])}
+}
+
+// Fetch copies rows firstRow .. firstRow+nRows-1 of both matrices to the host, nRows * nB cells each (bsk_compare_fetch).
+func (m *Compare) Fetch(firstRow, nRows uint64) (shared, total []uint32, err error) {
+	_, nB, _ := m.Info()
+	cells := nRows * nB
+	shared = make([]uint32, cells+1)
+	total = make([]uint32, cells+1)
+	rc := C.bsk_compare_fetch(m.eng.ctx, m.h, C.uint64_t(firstRow), C.uint64_t(nRows), (*C.uint32_t)(unsafe.Pointer(&shared[0])),
+		(*C.uint32_t)(unsafe.Pointer(&total[0])), C.uint64_t(cells))
+	runtime.KeepAlive(m)
+	return shared[:cells], total[:cells], m.eng.err(rc)
+}
+
+// Device returns the device addresses of the two matrices (bsk_compare_device).
+func (m *Compare) Device() (shared, total unsafe.Pointer) {
+	var s, t *C.uint32_t
+	C.bsk_compare_device(m.h, &s, &t)
+	runtime.KeepAlive(m)
+	return unsafe.Pointer(s), unsafe.Pointer(t)
+}
+
+// Close releases the device arrays now instead of at finalisation.
+func (m *Compare) Close() {
+	C.bsk_compare_release(m.h)
+	m.h = nil
+}
+
+// Jaccard returns Shared / Total of every cell, row-major, 0 where Total is 0.
+func (m *Compare) Jaccard() ([]float64, error) {
+	nA, _, _ := m.Info()
+	shared, total, err := m.Fetch(0, nA)
+	if err != nil {
+		return nil, err
+	}
+	j := make([]float64, len(shared))
+	for i := range j {
+		if total[i] != 0 {
+			j[i] = float64(shared[i]) / float64(total[i])
+		}
+	}
+	return j, nil
+}
+
+// MashDistance returns, with j the Jaccard of a cell, 1 where j is 0 and max(0, -ln(2j / (1 + j)) / k) elsewhere.
+func (m *Compare) MashDistance(k int) ([]float64, error) {
+	j, err := m.Jaccard()
+	if err != nil {
+		return nil, err
+	}
+	for i, x := range j {
+		if x == 0 {
+			j[i] = 1
+		} else {
+			j[i] = math.Max(0, -math.Log(2*x/(1+x))/float64(k))
+		}
+	}
+	return j, nil
+}

@@ -177,6 +177,13 @@ SYMBOLS = [
     ("bsk_sets_op_counted", C.c_int, [_vp, _vp, _vp, C.c_int, _pp]),
     ("bsk_sets_filter_counts", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _pp]),
     ("bsk_sets_totals", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp]),
+    ("bsk_sets_bottom", C.c_int, [_vp, _vp, C.c_uint64, _pp]),
+    ("bsk_sets_compare", C.c_int, [_vp, _vp, _vp, C.c_uint64, _pp]),
+    ("bsk_compare_info", C.c_int, [_vp, _u64p, _u64p, _u64p]),
+    ("bsk_compare_plan", C.c_int, [_vp, C.POINTER(C.c_char_p), _u64p]),
+    ("bsk_compare_fetch", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64]),
+    ("bsk_compare_device", C.c_int, [_vp, _pp, _pp]),
+    ("bsk_compare_release", None, [_vp]),
 ]
 SETS_PER_SEQUENCE, SETS_WHOLE_BATCH = 0, 1
 SETOP_UNION, SETOP_INTERSECT, SETOP_DIFF, SETOP_SYMDIFF = 0, 1, 2, 3

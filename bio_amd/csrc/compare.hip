@@ -1,0 +1,372 @@
+// compare.hip -- MinHash on the device: bottom-n sets (bsk_sets_bottom) and the dense all-pairs comparison (bsk_sets_compare), what
+// mash dist / triangle, sourmash compare, dereplication and clustering start from.
+//
+// k_cmp_tile.  A GEMM-shaped problem whose inner product is a merge of two sorted u64 lists.  A workgroup owns a tile of
+// CMP_ROWS x CMP_COLS pairs, one lane per pair; the tile's CMP_ROWS + CMP_COLS sets pass through LDS once per tile, not once per pair.
+// The pairs advance through their sets at different rates, so the sets are staged BY VALUE RANGE, in rounds.  Every set of the tile
+// has an effective prefix of min(limit, size) values (no pair can walk past the limit-th value of either set) and a cursor.  A round:
+//   v_hi     among the sets with more than CMP_WINDOW unstaged values, the smallest value[cursor + CMP_WINDOW]; when no set has that
+//            many left this is the tile's last round and everything left is staged (a flag: any u64 is a legal value)
+//   staging  every set's next min(left, CMP_WINDOW) values go to its LDS window, then a binary search in the window keeps the values
+//            < v_hi: at most CMP_WINDOW of them, because value[cursor + CMP_WINDOW] >= v_hi.  The cursor moves past them.
+//   merging  both windows of a pair are complete inside the round's value range, so the lane merges them to their ends: no per-pair
+//            cursor survives the round, and once one window is exhausted the rest of the other is counted without being read.  A lane
+//            whose total has reached the limit does nothing more.  Window ends are indices, never values.
+// The set that fixed v_hi advances by a full window, so every round makes progress.  The tile stops after its last round, or as soon
+// as every pair of the tile has reached the limit.
+// LDS layout: a-window r at s_a[r * CMP_WINDOW + j]: the 16 lanes of a row read one address (broadcast), a 32-lane half holds two
+// rows.  b-window c interleaved, s_b[j * CMP_COLS + c]: ds_read_b64 banks are (slot mod 32) = (j & 1) * 16 + c, so the lanes of a row
+// -- different c, any j -- never meet on a bank, and the two rows of a half at most 2-way.  The staging thread (j, c) = (k * 16 + t / 16,
+// t % 16) writes s_b[k * 256 + t]: consecutive, conflict-free.
+//
+// bsk_sets_bottom: the sizes min(n, size) through the library's scan, then a gather by groups of lanes (8 per set while the kept sets
+// average at most CMP_BT_SMALL values, else a wavefront per set).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <new>
+
+#include "biosketch.h"
+#include "host_types.hpp"
+#include "sets_internal.hpp"
+
+#define CMP_ROWS 16             // a-sets of a tile
+#define CMP_COLS 16             // b-sets of a tile
+#define CMP_WINDOW 128          // values of a set staged per round: 32 windows x 128 x 8 B = 32 KB of LDS, four workgroups a CU
+#define CMP_BLOCKS_PER_CU 4     // the tile grid's cap
+#define CMP_BT_SMALL 16         // bsk_sets_bottom: kept values per set (average) up to which a set takes 8 lanes
+#define CMP_BT_BLOCKS_PER_CU 16 // ... and its gather's cap
+#define CMP_THREADS (CMP_ROWS * CMP_COLS)
+#define CMP_SETS (CMP_ROWS + CMP_COLS)
+
+struct bsk_compare {
+    bsk_ctx *ctx = nullptr;
+    u64 n_a = 0, n_b = 0, limit = 0;
+    u32 *shared = nullptr, *total = nullptr;  // [n_a * n_b] row-major
+    size_t c_shared = 0, c_total = 0;         // bytes allocated (grow-only)
+    char plan[256] = "";
+    u64 figures[3] = {};  // tiles run, rounds summed over the tiles, most rounds of one tile
+};
+
+namespace {
+
+static_assert(CMP_THREADS == 256 && CMP_THREADS / CMP_COLS == CMP_ROWS && CMP_SETS <= 64, "one lane per pair; the first wavefront keeps the sets' cursors");
+static_assert(CMP_WINDOW % CMP_ROWS == 0 && (CMP_ROWS * CMP_WINDOW) % CMP_THREADS == 0, "the staging loops have no tail");
+
+__global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile(const u64 *aoff, const u64 *av, u64 n_a, const u64 *boff, const u64 *bv, u64 n_b, u32 lim, u64 ntiles,
+                                                         u64 tiles_x, u32 *shared, u32 *total, u64 *fig) {
+    __shared__ u64 s_a[CMP_ROWS * CMP_WINDOW];
+    __shared__ u64 s_b[CMP_COLS * CMP_WINDOW];
+    __shared__ u64 s_from[CMP_SETS];  // the set's first unstaged value (index into av / bv)
+    __shared__ u32 s_n[CMP_SETS];     // values copied to its window this round
+    __shared__ u32 s_cnt[CMP_SETS];   // ... and how many of them lie below v_hi: the window's end
+    __shared__ int s_last;
+    const int t = threadIdx.x, r = t / CMP_COLS, c = t % CMP_COLS;
+    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const u64 i0 = (tile / tiles_x) * CMP_ROWS, j0 = (tile % tiles_x) * CMP_COLS;
+        // threads 0 .. CMP_SETS - 1 keep a set each: rows first, then columns
+        const u64 *vals = t < CMP_ROWS ? av : bv;
+        u64 base = 0;
+        u32 len = 0, start = 0;
+        if (t < CMP_SETS) {
+            const bool isa = t < CMP_ROWS;
+            const u64 g = isa ? i0 + t : j0 + (t - CMP_ROWS);
+            const u64 *off = isa ? aoff : boff;
+            if (g < (isa ? n_a : n_b)) {
+                base = off[g];
+                const u64 sz = off[g + 1] - base;
+                len = sz < (u64)lim ? (u32)sz : lim;
+            }
+        }
+        const bool pair = i0 + r < n_a && j0 + c < n_b;
+        u32 tot = 0, sh = 0, rounds = 0;
+        for (;;) {
+            u64 cand = 0;
+            bool has = false;
+            if (t < CMP_SETS) {
+                const u32 rem = len - start;
+                has = rem > CMP_WINDOW;
+                s_from[t] = base + start;
+                s_n[t] = has ? CMP_WINDOW : rem;
+                if (has) cand = vals[base + start + CMP_WINDOW];
+            }
+            __syncthreads();
+            // staging: a-windows row by row (a wavefront copies 64 consecutive values), b-windows interleaved
+#pragma unroll
+            for (int k = 0; k < CMP_ROWS * CMP_WINDOW / CMP_THREADS; ++k) {
+                const int idx = k * CMP_THREADS + t, s = idx / CMP_WINDOW, j = idx % CMP_WINDOW;
+                if ((u32)j < s_n[s]) s_a[idx] = av[s_from[s] + j];
+            }
+#pragma unroll
+            for (int k = 0; k < CMP_WINDOW / CMP_ROWS; ++k) {
+                const int j = k * CMP_ROWS + r;
+                if ((u32)j < s_n[CMP_ROWS + c]) s_b[k * CMP_THREADS + t] = bv[s_from[CMP_ROWS + c] + j];
+            }
+            __syncthreads();
+            if (t < 64) {  // the first wavefront: v_hi, the windows' ends, the cursors
+                const bool any = __ballot(has) != 0;
+                u64 vhi = has ? cand : ~0ull;  // (lanes without a candidate never undercut one; `any` says whether there is one)
+                for (int d = 32; d; d >>= 1) {
+                    const u64 o = __shfl_xor(vhi, d, 64);
+                    vhi = o < vhi ? o : vhi;
+                }
+                if (t < CMP_SETS) {
+                    u32 cnt = s_n[t];
+                    if (any) {  // the values below v_hi
+                        u32 lo = 0, hi = cnt;
+                        while (lo < hi) {
+                            const u32 mid = (lo + hi) >> 1;
+                            const u64 v = t < CMP_ROWS ? s_a[t * CMP_WINDOW + mid] : s_b[mid * CMP_COLS + (t - CMP_ROWS)];
+                            if (v < vhi) lo = mid + 1;
+                            else hi = mid;
+                        }
+                        cnt = lo;
+                    }
+                    s_cnt[t] = cnt;
+                    start += cnt;
+                }
+                if (t == 0) s_last = any ? 0 : 1;
+            }
+            __syncthreads();
+            ++rounds;
+            if (pair && tot < lim) {
+                const u32 ea = s_cnt[r], eb = s_cnt[CMP_ROWS + c];
+                u32 ia = 0, ib = 0;
+                if (ea && eb) {
+                    u64 x = s_a[r * CMP_WINDOW], y = s_b[c];
+                    for (;;) {
+                        ++tot;
+                        const bool le = x <= y, ge = x >= y;
+                        sh += (le && ge) ? 1u : 0u;
+                        ia += le ? 1u : 0u;
+                        ib += ge ? 1u : 0u;
+                        if (tot >= lim || ia >= ea || ib >= eb) break;
+                        if (le) x = s_a[r * CMP_WINDOW + ia];
+                        if (ge) y = s_b[ib * CMP_COLS + c];
+                    }
+                }
+                // one window is exhausted: what the other still holds lies inside the round's range and is not in the first
+                const u32 rest = (ea - ia) + (eb - ib), room = lim - tot;
+                tot += rest < room ? rest : room;
+            }
+            const int last = s_last;
+            if (!__syncthreads_or(pair && tot < lim) || last) break;
+        }
+        if (pair) {
+            const u64 cell = (i0 + r) * n_b + j0 + c;
+            shared[cell] = sh;
+            total[cell] = tot;
+        }
+        if (t == 0) {
+            atomicAdd((unsigned long long *)&fig[0], 1ull);
+            atomicAdd((unsigned long long *)&fig[1], (unsigned long long)rounds);
+            atomicMax((unsigned long long *)&fig[2], (unsigned long long)rounds);
+        }
+    }
+}
+
+// ---- bsk_sets_bottom ----
+struct BtSize {  // what set r keeps
+    const u64 *offs;
+    u64 n;
+    __device__ __forceinline__ u64 operator()(u64 r) const {
+        const u64 s = offs[r + 1] - offs[r];
+        return s < n ? s : n;
+    }
+};
+template <int LANES>
+__global__ __launch_bounds__(256) void k_bt_gather(const u64 *ioff, const u64 *iv, const u32 *ic, const u64 *ooff, u64 n_sets, u64 *ov, u32 *oc) {
+    const u64 lane = threadIdx.x % LANES;
+    for (u64 s = ((u64)blockIdx.x * 256 + threadIdx.x) / LANES; s < n_sets; s += (u64)gridDim.x * (256 / LANES)) {
+        const u64 src = ioff[s], dst = ooff[s], cnt = ooff[s + 1] - dst;
+        for (u64 j = lane; j < cnt; j += LANES) {
+            ov[dst + j] = iv[src + j];
+            if (ic) oc[dst + j] = ic[src + j];
+        }
+    }
+}
+
+hipError_t cmp_pool(bsk_ctx *ctx, int slot, size_t bytes, void **out) {  // slots 45-46: the context's grow-only temporaries of this file
+    if (ctx->tmp_cap[slot] < bytes || !ctx->tmp[slot]) {
+        (void)hipFree(ctx->tmp[slot]);
+        ctx->tmp[slot] = nullptr;
+        ctx->tmp_cap[slot] = 0;
+        const size_t want = bytes + bytes / 4 + 256;
+        const hipError_t e = hipMalloc(&ctx->tmp[slot], want);
+        if (e != hipSuccess) return e;
+        ctx->tmp_cap[slot] = want;
+    }
+    *out = ctx->tmp[slot];
+    return hipSuccess;
+}
+template <class T>
+hipError_t cmp_grow(T **p, size_t *cap, size_t bytes) {  // an object's own arrays: grow-only
+    if (*cap >= bytes && *p) return hipSuccess;
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const size_t want = bytes + bytes / 4 + 256;
+    const hipError_t e = hipMalloc(p, want);
+    if (e == hipSuccess) *cap = want;
+    return e;
+}
+
+int bottom_impl(bsk_ctx *ctx, const bsk_sets *s, u64 n, bsk_sets *res) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const u64 G = s->n_sets;
+    res->n_sets = G;
+    res->n_values = 0;
+    res->counted = false;
+    res->plan[0] = 0;
+    res->by_path[0] = res->by_path[1] = res->by_path[2] = 0;
+    HIPCHK(ctx, cmp_grow(&res->offsets, &res->c_offsets, (G + 1) * 8));
+    void *bq = nullptr;
+    HIPCHK(ctx, cmp_pool(ctx, 46, ((G + SCAN_CHUNK - 1) / SCAN_CHUNK + 2 + 8) * 8, &bq));
+    u64 *tot = static_cast<u64 *>(bq), *part = tot + 8;
+    HIPCHK(ctx, hipMemsetAsync(tot, 0, 64, st));
+    HIPCHK(ctx, scan_counts(st, BtSize{s->offsets, n}, G, part, res->offsets, tot, (u64 *)nullptr));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const u64 M = ctx->h_pinned[0];
+    HIPCHK(ctx, cmp_grow(&res->values, &res->c_values, (M ? M : 1) * 8));
+    if (s->counted) HIPCHK(ctx, sets_grow_counts(res, M ? M : 1, true));
+    if (M) {
+        const u32 *ic = s->counted ? s->counts : nullptr;
+        const bool small = M <= G * CMP_BT_SMALL;
+        const u64 per_block = small ? 256 / 8 : 256 / 64;
+        const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>((G + per_block - 1) / per_block, (u64)ctx->cus * CMP_BT_BLOCKS_PER_CU));
+        if (small) hipLaunchKernelGGL(k_bt_gather<8>, dim3(grid), dim3(256), 0, st, s->offsets, s->values, ic, res->offsets, G, res->values, res->counts);
+        else hipLaunchKernelGGL(k_bt_gather<64>, dim3(grid), dim3(256), 0, st, s->offsets, s->values, ic, res->offsets, G, res->values, res->counts);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipStreamSynchronize(st));
+    }
+    res->n_values = M;
+    res->counted = s->counted;
+    return BSK_OK;
+}
+
+int compare_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit, bsk_compare *res) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const u64 n_a = a->n_sets, n_b = b->n_sets, cells = n_a * n_b;
+    res->n_a = n_a;
+    res->n_b = n_b;
+    res->limit = limit;
+    res->figures[0] = res->figures[1] = res->figures[2] = 0;
+    HIPCHK(ctx, cmp_grow(&res->shared, &res->c_shared, (cells ? cells : 1) * 4));
+    HIPCHK(ctx, cmp_grow(&res->total, &res->c_total, (cells ? cells : 1) * 4));
+    if (cells == 0) {
+        snprintf(res->plan, sizeof res->plan, "bsk_sets_compare: no pairs");
+        return BSK_OK;
+    }
+    void *bf = nullptr;
+    HIPCHK(ctx, cmp_pool(ctx, 45, 64, &bf));
+    u64 *fig = static_cast<u64 *>(bf);
+    HIPCHK(ctx, hipMemsetAsync(fig, 0, 64, st));
+    const u64 tiles_x = (n_b + CMP_COLS - 1) / CMP_COLS, ntiles = ((n_a + CMP_ROWS - 1) / CMP_ROWS) * tiles_x;
+    // the inputs hold fewer than 2^32 values together, so no total reaches 2^32 - 1 before its union ends
+    const u32 lim = limit == 0 || limit > 0xffffffffull ? 0xffffffffu : (u32)limit;
+    const unsigned grid = (unsigned)std::min<u64>(ntiles, (u64)ctx->cus * CMP_BLOCKS_PER_CU);
+    hipLaunchKernelGGL(k_cmp_tile, dim3(grid), dim3(CMP_THREADS), 0, st, (const u64 *)a->offsets, (const u64 *)a->values, n_a, (const u64 *)b->offsets, (const u64 *)b->values, n_b,
+                       lim, ntiles, tiles_x, res->shared, res->total, fig);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, fig, 24, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    for (int i = 0; i < 3; ++i) res->figures[i] = ctx->h_pinned[i];
+    snprintf(res->plan, sizeof res->plan, "bsk_sets_compare: k_cmp_tile, %llu x %llu pairs in %llu tiles of %d x %d, windows of %d values, limit %llu", (unsigned long long)n_a,
+             (unsigned long long)n_b, (unsigned long long)ntiles, CMP_ROWS, CMP_COLS, CMP_WINDOW, (unsigned long long)limit);
+    return BSK_OK;
+}
+
+}  // namespace
+
+extern "C" void bsk_compare_release(bsk_compare *c) {
+    if (!c) return;
+    if (c->ctx) (void)hipSetDevice(c->ctx->device);
+    (void)hipFree(c->shared);
+    (void)hipFree(c->total);
+    delete c;
+}
+
+extern "C" int bsk_sets_bottom(bsk_ctx *ctx, const bsk_sets *s, uint64_t n, bsk_sets **out) {
+    if (!ctx || !s || !out) return fail_arg(ctx, "bsk_sets_bottom: null argument");
+    if (s->ctx != ctx || (*out && (*out)->ctx != ctx)) return fail_arg(ctx, "bsk_sets_bottom: the sets belong to another context");
+    if (*out == s) return fail_arg(ctx, "bsk_sets_bottom: *out is the input");
+    if (n == 0) return fail_arg(ctx, "bsk_sets_bottom: n == 0");
+    bsk_sets *res = *out;
+    *out = nullptr;
+    if (!res) res = new (std::nothrow) bsk_sets();
+    if (!res) return BSK_ERR_NOMEM;
+    res->ctx = ctx;
+    const int rc = bottom_impl(ctx, s, n, res);
+    if (rc != BSK_OK) {
+        bsk_sets_release(res);
+        return rc;
+    }
+    *out = res;
+    return BSK_OK;
+}
+
+extern "C" int bsk_sets_compare(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, uint64_t limit, bsk_compare **cmp) {
+    if (!ctx || !a || !b || !cmp) return fail_arg(ctx, "bsk_sets_compare: null argument");
+    if (a->ctx != ctx || b->ctx != ctx || (*cmp && (*cmp)->ctx != ctx)) return fail_arg(ctx, "bsk_sets_compare: the sets or the result belong to another context");
+    bsk_compare *res = *cmp;
+    *cmp = nullptr;
+    // both limits before anything is allocated (a == b holds its values once)
+    const u64 held = a == b ? a->n_values : a->n_values + b->n_values;
+    const bool many_values = a->n_values >= (1ULL << 32) || b->n_values >= (1ULL << 32) || held >= (1ULL << 32);
+    const bool many_cells = a->n_sets && b->n_sets > (1ULL << 31) / a->n_sets;
+    if (many_values || many_cells) {
+        bsk_compare_release(res);
+        ctx->err = many_values ? "bsk_sets_compare: 2^32 values or more (split the sets)" : "bsk_sets_compare: more than 2^31 cells (split the sets)";
+        return BSK_ERR_UNSUPPORTED;
+    }
+    if (!res) res = new (std::nothrow) bsk_compare();
+    if (!res) return BSK_ERR_NOMEM;
+    res->ctx = ctx;
+    const int rc = compare_impl(ctx, a, b, limit, res);
+    if (rc != BSK_OK) {
+        bsk_compare_release(res);
+        return rc;
+    }
+    *cmp = res;
+    return BSK_OK;
+}
+
+extern "C" int bsk_compare_info(const bsk_compare *c, uint64_t *n_a, uint64_t *n_b, uint64_t *limit) {
+    if (!c) return BSK_ERR_ARG;
+    if (n_a) *n_a = c->n_a;
+    if (n_b) *n_b = c->n_b;
+    if (limit) *limit = c->limit;
+    return BSK_OK;
+}
+
+extern "C" int bsk_compare_plan(const bsk_compare *c, const char **plan, uint64_t figures[3]) {
+    if (!c) return BSK_ERR_ARG;
+    if (plan) *plan = c->plan;
+    if (figures)
+        for (int i = 0; i < 3; ++i) figures[i] = c->figures[i];
+    return BSK_OK;
+}
+
+extern "C" int bsk_compare_fetch(bsk_ctx *ctx, const bsk_compare *c, uint64_t first_row, uint64_t n_rows, uint32_t *shared, uint32_t *total, uint64_t cell_cap) {
+    if (!ctx || !c) return fail_arg(ctx, "bsk_compare_fetch: null argument");
+    if (c->ctx != ctx) return fail_arg(ctx, "bsk_compare_fetch: the result belongs to another context");
+    if (first_row > c->n_a || n_rows > c->n_a - first_row) return fail_arg(ctx, "bsk_compare_fetch: rows outside the matrix");
+    const u64 cells = n_rows * c->n_b;  // (at most 2^31)
+    if (cells > cell_cap) return fail_arg(ctx, "bsk_compare_fetch: cell_cap too small");
+    if (cells == 0 || (!shared && !total)) return BSK_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (shared) HIPCHK(ctx, hipMemcpyAsync(shared, c->shared + first_row * c->n_b, cells * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (total) HIPCHK(ctx, hipMemcpyAsync(total, c->total + first_row * c->n_b, cells * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return BSK_OK;
+}
+
+extern "C" int bsk_compare_device(const bsk_compare *c, const uint32_t **shared, const uint32_t **total) {
+    if (!c) return BSK_ERR_ARG;
+    if (shared) *shared = c->shared;
+    if (total) *total = c->total;
+    return BSK_OK;
+}

@@ -48,7 +48,7 @@ struct bsk_ctx {
     u8 *d_lut = nullptr;      // codon tables of `lut_table` (kernels_translate.hpp layout)
     int lut_table = 0;
     // tiled calls: grow-only temporaries (hipMalloc / hipFree of ten buffers per call cost more than the kernels)
-    void *tmp[48] = {};      // 0-9: tiled calls / sets, 12-14: bsk_result_fetch, 16-19: bsk_result_compact, 20: bsk_sets_fetch_narrow, 21-23: class plans, 24-27: two-pass syncmers, 28-29: the ASCII side launch's own reference words / status bytes, 32-37: set operations (setops.hip), 40-44: counted sets (counts.hip)
+    void *tmp[48] = {};      // 0-9: tiled calls / sets, 12-14: bsk_result_fetch, 16-19: bsk_result_compact, 20: bsk_sets_fetch_narrow, 21-23: class plans, 24-27: two-pass syncmers, 28-29: the ASCII side launch's own reference words / status bytes, 32-37: set operations (setops.hip), 40-44: counted sets (counts.hip), 45-46: all-pairs comparison / bottom-n (compare.hip)
     size_t tmp_cap[48] = {};
     u64 *h_refs = nullptr;   // pinned staging of bsk_result_fetch (refs down, offsets up), grow-only
     size_t h_refs_cap = 0;

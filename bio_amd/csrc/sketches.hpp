@@ -242,6 +242,36 @@ class DeviceSets : public Owned<bsk_sets, bsk_sets_release> {
         out.resize(n);
         return rc;
     }
+
+    // ---- MinHash: every set of s cut to its min(n, size) smallest values (counts ride along) INTO this object, as op() ----
+    int bottom(Engine &e, const DeviceSets &s, uint64_t n) { return bsk_sets_bottom(e.ctx(), s.get(), n, &p_); }
+};
+
+// dense all-pairs comparison (bsk_compare): shared[n_a * n_b] and total[n_a * n_b], row-major
+class SetsCompare : public Owned<bsk_compare, bsk_compare_release> {
+   public:
+    // every set of a against every set of b INTO this object (empty, or the result of an earlier compare on this engine: arrays kept,
+    // grow only); limit: the distinct values of a pair's union that are walked (0: all -- the exact Jaccard; n: the Mash estimator)
+    int compare(Engine &e, const DeviceSets &a, const DeviceSets &b, uint64_t limit = 0) { return bsk_sets_compare(e.ctx(), a.get(), b.get(), limit, &p_); }
+    int info(uint64_t &n_a, uint64_t &n_b, uint64_t &limit) const { return bsk_compare_info(p_, &n_a, &n_b, &limit); }
+    // figures: tiles run, rounds summed over the tiles, most rounds of one tile
+    const char *plan(uint64_t figures[3]) const {
+        const char *d = "";
+        bsk_compare_plan(p_, &d, figures);
+        return d;
+    }
+    int fetch(Engine &e, std::vector<uint32_t> &shared, std::vector<uint32_t> &total) const {
+        uint64_t n_a = 0, n_b = 0;
+        int rc = bsk_compare_info(p_, &n_a, &n_b, nullptr);
+        if (rc != BSK_OK) return rc;
+        shared.assign(n_a * n_b + 1, 0);
+        total.assign(n_a * n_b + 1, 0);
+        rc = bsk_compare_fetch(e.ctx(), p_, 0, n_a, shared.data(), total.data(), n_a * n_b);
+        shared.resize(n_a * n_b);
+        total.resize(n_a * n_b);
+        return rc;
+    }
+    void device(const uint32_t *&shared, const uint32_t *&total) const { bsk_compare_device(p_, &shared, &total); }
 };
 
 // hits of a search (bsk_hits): CSR by query, target ids ascending inside a query

@@ -379,6 +379,26 @@ class Sets:
         self.eng._chk(self.eng.lib.bsk_sets_totals(self.eng.ctx, self.h, 0, ns, t.ctypes.data))
         return t[:ns]
 
+    # -- MinHash (bsk_sets_bottom / bsk_sets_compare)
+    def bottom(self, n: int, into: Optional["Sets"] = None) -> "Sets":
+        """Every set cut to its min(n, size) smallest values, counts included when the sets are counted (bsk_sets_bottom): the
+        fixed-size MinHash sketch.  into as in op()."""
+        return self._into(into, lambda out: self.eng.lib.bsk_sets_bottom(self.eng.ctx, self.h, n, out))
+
+    def compare(self, other: Optional["Sets"] = None, limit: int = 0, reuse: Optional["Compare"] = None) -> "Compare":
+        """Every set of self against every set of other (None: of self): per pair the first `limit` distinct values of the union
+        (0: all of them) and how many of those both sets hold (bsk_sets_compare).  limit 0 gives the exact Jaccard, limit n the
+        Mash estimator of bottom-n sketches.  reuse: the Compare of an earlier call on this engine, whose device arrays are kept."""
+        other = self if other is None else other
+        h = reuse.h if reuse is not None and reuse.h else C.c_void_p()
+        rc = self.eng.lib.bsk_sets_compare(self.eng.ctx, self.h, other.h, limit, C.byref(h))
+        if reuse is not None:
+            reuse.h = h if h.value else None  # (kept on an argument error, released by the library on any other)
+        self.eng._chk(rc)
+        res = reuse if reuse is not None else Compare(self.eng)
+        res._bind(h, np.diff(self.offsets()))
+        return res
+
     def plan(self):
         """What made these sets (bsk_sets_plan): a description and the pairs of the last op() that took the group, wave and tiled
         path; sets of any other origin report an empty string and zeros."""
@@ -389,6 +409,90 @@ class Sets:
     def close(self):
         if self.h:
             self.eng.lib.bsk_sets_release(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Compare:
+    """Dense all-pairs comparison (bsk_compare): shared[n_a, n_b] and total[n_a, n_b] (u32), fetched on first use."""
+
+    def __init__(self, eng: "Engine"):
+        self.eng, self.h = eng, None
+        self._host = None
+
+    def _bind(self, h, a_sizes: np.ndarray):
+        self.h, self._host = h, None
+        self.a_sizes = a_sizes.astype(np.uint64)
+
+    def info(self):
+        na, nb, lim = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self.eng._chk(self.eng.lib.bsk_compare_info(self.h, C.byref(na), C.byref(nb), C.byref(lim)))
+        return dict(n_a=na.value, n_b=nb.value, limit=lim.value)
+
+    def plan(self):
+        """What the comparison ran (bsk_compare_plan): a description, the tiles run, the rounds summed over them, the most of one tile."""
+        p, n = C.c_char_p(), (C.c_uint64 * 3)()
+        self.eng._chk(self.eng.lib.bsk_compare_plan(self.h, C.byref(p), n))
+        return dict(plan=(p.value or b"").decode(), tiles=int(n[0]), rounds=int(n[1]), max_rounds=int(n[2]))
+
+    def device(self):
+        """bsk_compare_device -> (shared_ptr, total_ptr)"""
+        ps, pt = C.c_void_p(), C.c_void_p()
+        self.eng._chk(self.eng.lib.bsk_compare_device(self.h, C.byref(ps), C.byref(pt)))
+        return ps.value, pt.value
+
+    def fetch(self, first_row: int = 0, n_rows: Optional[int] = None):
+        """bsk_compare_fetch -> (shared[n_rows, n_b], total[n_rows, n_b])"""
+        inf = self.info()
+        if n_rows is None:
+            n_rows = inf["n_a"] - first_row
+        cells = max(n_rows, 0) * inf["n_b"]
+        sh, tt = np.zeros(max(cells, 1), np.uint32), np.zeros(max(cells, 1), np.uint32)
+        self.eng._chk(self.eng.lib.bsk_compare_fetch(self.eng.ctx, self.h, first_row, n_rows, sh.ctypes.data, tt.ctypes.data, cells))
+        return sh[:cells].reshape(n_rows, inf["n_b"]), tt[:cells].reshape(n_rows, inf["n_b"])
+
+    def _cache(self):
+        if self._host is None:
+            self._host = self.fetch()
+        return self._host
+
+    @property
+    def shared(self) -> np.ndarray:
+        return self._cache()[0]
+
+    @property
+    def total(self) -> np.ndarray:
+        return self._cache()[1]
+
+    def jaccard(self) -> np.ndarray:
+        """shared / total as float64, 0.0 where total == 0"""
+        s, t = self.shared.astype(np.float64), self.total.astype(np.float64)
+        return np.divide(s, t, out=np.zeros_like(s), where=t != 0)
+
+    def containment(self) -> np.ndarray:
+        """shared / |a[i]| (0.0 for an empty a[i]); whole sets only: limit == 0"""
+        if self.info()["limit"] != 0:
+            raise ValueError("containment is defined on whole sets: compare with limit=0")
+        s = self.shared.astype(np.float64)
+        q = np.broadcast_to(self.a_sizes.astype(np.float64)[:, None], s.shape)
+        return np.divide(s, q, out=np.zeros_like(s), where=q != 0)
+
+    def mash_distance(self, k: int) -> np.ndarray:
+        """1.0 where the Jaccard j is 0, elsewhere max(0, -ln(2j / (1 + j)) / k)"""
+        j = self.jaccard()
+        d = np.ones_like(j)
+        nz = j > 0
+        d[nz] = np.maximum(0.0, -np.log(2.0 * j[nz] / (1.0 + j[nz])) / k)
+        return d
+
+    def close(self):
+        if self.h:
+            self.eng.lib.bsk_compare_release(self.h)
             self.h = None
 
     def __del__(self):

@@ -630,6 +630,45 @@ int bsk_sets_filter_counts(bsk_ctx *ctx, const bsk_sets *s, uint32_t min_count, 
 /* per set of the range the sum of its counts (u64: exact); an uncounted object gives the sets' sizes */
 int bsk_sets_totals(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t count, uint64_t *totals /* host */);
 
+/* ---- MinHash: bottom-n sets, all-pairs comparison ----
+ * bsk_sets_bottom: out[i] is the min(n, |s[i]|) smallest values of s[i] -- the fixed-size (Mash, sourmash num=) sketch; the sets are
+ * ascending, so these are a prefix.  A counted input yields a counted output with the counts of the kept values, an uncounted input an
+ * uncounted output.  n == 0 is BSK_ERR_ARG.  *out as in bsk_sets_reduce: NULL, or the object of an earlier op on this context (arrays
+ * kept, grow only); *out == s is BSK_ERR_ARG; an argument error leaves *out as it was, any other error releases it and sets *out to
+ * NULL.  The result is an ordinary bsk_sets: index it, search it, fetch it, use it in the algebra.
+ *
+ * bsk_sets_compare: for every pair (i, j), i < n_a, j < n_b, walk the distinct values of a[i] | b[j] in ascending order and stop after
+ * `limit` of them (limit == 0: never stop early).  total[i * n_b + j] is the number walked, min(limit, |a[i] | b[j]|);
+ * shared[i * n_b + j] is how many of the walked values both sets hold.  Both are dense row-major u32 matrices on the device.
+ *   limit == 0: shared is |a & b| and total is |a | b| -- the exact Jaccard shared / total;
+ *   limit == n: shared / total is the Mash estimator of the Jaccard from bottom-n sketches;
+ *   only the `limit` smallest values of each set can take part, so the result on full sets equals the result on their
+ *   bsk_sets_bottom(limit).
+ * Any u64 is a legal value, 0 and 2^64-1 included.  a == b (the same object) is legal; the full matrix is computed.  n_a == 0 or
+ * n_b == 0 gives an empty result with BSK_OK.  a and b must belong to ctx.  Inputs that together hold 2^32 values or more (a == b:
+ * counted once), or more than 2^31 cells, are BSK_ERR_UNSUPPORTED; both are checked before anything is allocated.  *cmp: NULL, or the
+ * object of an earlier compare on this context, whose device arrays are kept and only grow; error rules as bsk_index_search (an
+ * argument error leaves *cmp as it was, any other error releases it and sets *cmp to NULL).  Everything runs on the context's stream;
+ * the host reads back one block of figures.
+ * Which route for an all-against-all: this one is dense -- its cost is the cells times the values a pair walks, whatever the sets
+ * share -- and is the only one that gives the limit-bounded (Mash) numbers; it suits sketches of up to a few thousand values.
+ * bsk_index_build + bsk_index_search is output-sparse -- its cost follows the postings and the pairs that share something -- and suits
+ * whole sets (limit == 0 only) of many values of which most pairs share nothing.
+ * bsk_compare_plan: a short description that names the kernel and its tile shape; figures = {tiles run, rounds summed over the tiles,
+ * most rounds of one tile} (a round stages one window of values per set of a tile).
+ * bsk_compare_fetch: rows first_row .. first_row + n_rows - 1 to the host, n_rows * n_b cells each; BSK_ERR_ARG for a range outside
+ * the matrix, for more cells than cell_cap and for a foreign context. */
+int bsk_sets_bottom(bsk_ctx *ctx, const bsk_sets *s, uint64_t n, bsk_sets **out);
+
+typedef struct bsk_compare bsk_compare;
+int bsk_sets_compare(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, uint64_t limit, bsk_compare **cmp);
+int bsk_compare_info(const bsk_compare *c, uint64_t *n_a, uint64_t *n_b, uint64_t *limit);       /* any out-pointer may be NULL */
+int bsk_compare_plan(const bsk_compare *c, const char **plan, uint64_t figures[3]);              /* either may be NULL */
+int bsk_compare_fetch(bsk_ctx *ctx, const bsk_compare *c, uint64_t first_row, uint64_t n_rows,
+                      uint32_t *shared, uint32_t *total, uint64_t cell_cap);                      /* either array may be NULL */
+int bsk_compare_device(const bsk_compare *c, const uint32_t **shared, const uint32_t **total);
+void bsk_compare_release(bsk_compare *c);
+
 #ifdef __cplusplus
 }
 #endif
