@@ -57,6 +57,19 @@ def ref_search(t_offs, t_vals, q_offs, q_vals, min_shared=1, qc=0.0, tc=0.0):
     return ref_select(ref_counts(t_offs, t_vals, q_offs, q_vals), t_offs, q_offs, min_shared, qc, tc)
 
 
+def ref_top(o, t, s, n):
+    """np.lexsort((target, -shared)) inside every query (the query as the outermost key does all of them at once), cut at n"""
+    nq = len(o) - 1
+    cnt = np.diff(o).astype(np.int64)
+    q = np.repeat(np.arange(nq, dtype=np.int64), cnt)
+    order = np.lexsort((t, -s.astype(np.int64), q))
+    rank = np.arange(len(t), dtype=np.int64) - np.repeat(o[:-1].astype(np.int64), cnt)
+    idx = order[rank < n]
+    no = np.zeros(nq + 1, U64)
+    no[1:] = np.cumsum(np.minimum(cnt, n))
+    return no, t[idx], s[idx]
+
+
 def posting_sums(t_offs, t_vals, q_offs, q_vals):
     """every query's sum of posting counts: how many targets hold each of its values, added up"""
     sv = np.sort(t_vals)

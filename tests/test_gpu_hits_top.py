@@ -13,7 +13,7 @@ import pytest
 
 from bio_amd import _lib as L
 from tests import search_cases as SC
-from tests.search_cases import collection, ref_search
+from tests.search_cases import collection, ref_search, ref_top
 
 pytestmark = pytest.mark.gpu
 U64 = np.uint64
@@ -36,19 +36,6 @@ def one_pass():
     # queries: k_top_group (32 blocks x 16 per CU), k_top_select / k_top_lds (8 blocks x 4 waves x 64), k_top_classes and k_top_list
     # (8 blocks x 256); sort-path queries: k_top_emit (16 blocks x 4 waves); hits: k_top_place (16 x 256), k_top_maxshared (8 x 256)
     return dict(cus=cus, group=cus * 512, wave=cus * 2048, classes=cus * 2048, emit=cus * 64, place=cus * 4096, maxshared=cus * 2048)
-
-
-def ref_top(o, t, s, n):
-    """np.lexsort((target, -shared)) inside every query (the query as the outermost key does all of them at once), cut at n"""
-    nq = len(o) - 1
-    cnt = np.diff(o).astype(np.int64)
-    q = np.repeat(np.arange(nq, dtype=np.int64), cnt)
-    order = np.lexsort((t, -s.astype(np.int64), q))
-    rank = np.arange(len(t), dtype=np.int64) - np.repeat(o[:-1].astype(np.int64), cnt)
-    idx = order[rank < n]
-    no = np.zeros(nq + 1, U64)
-    no[1:] = np.cumsum(np.minimum(cnt, n))
-    return no, t[idx], s[idx]
 
 
 def branches(o, n):

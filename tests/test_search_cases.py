@@ -51,6 +51,12 @@ def test_ref_search_equals_brute_force(seed):
     assert np.array_equal(SC.posting_sums(*tg, *qs), [sum(sum(v in t for t in tsets) for v in q) for q in qsets])
 
 
+def test_ref_top_on_a_hand_made_case():
+    """query 0: shared 2 5 5 1 -> the two 5s by ascending target, then the 2; query 1: no hits; query 2: one hit"""
+    o, t, s = SC.ref_top(np.array([0, 4, 4, 5], U64), np.array([1, 3, 7, 9, 2], np.uint32), np.array([2, 5, 5, 1, 4], np.uint32), 3)
+    assert o.tolist() == [0, 3, 3, 4] and t.tolist() == [3, 7, 1, 2] and s.tolist() == [5, 5, 2, 4] and t.dtype == s.dtype == np.uint32
+
+
 def test_s2_matrix_equals_ref_search():
     offs, vals = SC.s2_case(n_sets=60, size=500, pool=20_000)
     m = SC.s2_matrix(offs, vals)
