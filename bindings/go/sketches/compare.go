@@ -10,6 +10,7 @@ package sketches
 import "C"
 
 import (
+	"errors"
 	"math"
 	"runtime"
 	"unsafe"
@@ -127,4 +128,74 @@ func (m *Compare) MashDistance(k int) ([]float64, error) {
 		}
 	}
 	return j, nil
+}
+
+// ---- abundance-weighted comparison of counted sets ------------------------------------------------------------------------
+//
+// a.CompareCounted(b, 0, nil) walks every pair as Compare does and keeps, over the walked values both sets hold, Dot = the sum of
+// the products of the two counts (saturating at 2^64-1) and MinSum = the sum of their minima.  Sets without counts count 1.
+
+// CompareCounted is Compare with the counts (bsk_sets_compare_counted); into may be the result of either kind of compare.
+func (a *Sets) CompareCounted(b *Sets, limit uint64, into *Compare) (*Compare, error) {
+	if b == nil {
+		b = a
+	}
+	if into == nil {
+		into = &Compare{eng: a.eng}
+		runtime.SetFinalizer(into, func(m *Compare) { C.bsk_compare_release(m.h) })
+	}
+	rc := C.bsk_sets_compare_counted(a.eng.ctx, a.h, b.h, C.uint64_t(limit), &into.h)
+	runtime.KeepAlive(a)
+	runtime.KeepAlive(b)
+	return into, a.eng.err(rc)
+}
+
+// Weights returns the device addresses of Dot and MinSum, both nil for an unweighted result (bsk_compare_weights_device).
+func (m *Compare) Weights() (dot, minSum unsafe.Pointer) {
+	var d, s *C.uint64_t
+	C.bsk_compare_weights_device(m.h, &d, &s)
+	runtime.KeepAlive(m)
+	return unsafe.Pointer(d), unsafe.Pointer(s)
+}
+
+// FetchWeights copies rows firstRow .. firstRow+nRows-1 of Dot and MinSum to the host (bsk_compare_fetch_weights); an
+// unweighted result is an error.
+func (m *Compare) FetchWeights(firstRow, nRows uint64) (dot, minSum []uint64, err error) {
+	_, nB, _ := m.Info()
+	cells := nRows * nB
+	dot = make([]uint64, cells+1)
+	minSum = make([]uint64, cells+1)
+	rc := C.bsk_compare_fetch_weights(m.eng.ctx, m.h, C.uint64_t(firstRow), C.uint64_t(nRows), (*C.uint64_t)(unsafe.Pointer(&dot[0])),
+		(*C.uint64_t)(unsafe.Pointer(&minSum[0])), C.uint64_t(cells))
+	runtime.KeepAlive(m)
+	return dot[:cells], minSum[:cells], m.eng.err(rc)
+}
+
+// Cosine returns Dot / (sqrt(sumSqA[i]) * sqrt(sumSqB[j])) of every cell, row-major, with the operands' (*Sets).SumSq: 0 where a
+// norm is 0, NaN where Dot or either norm is saturated.  Whole sets only: a limit other than 0 is an error.
+func (m *Compare) Cosine(sumSqA, sumSqB []uint64) ([]float64, error) {
+	nA, nB, limit := m.Info()
+	if limit != 0 {
+		return nil, errors.New("Cosine: defined on whole sets, CompareCounted with limit 0")
+	}
+	if uint64(len(sumSqA)) != nA || uint64(len(sumSqB)) != nB {
+		return nil, errors.New("Cosine: one squared norm per set of either operand")
+	}
+	dot, _, err := m.FetchWeights(0, nA)
+	if err != nil {
+		return nil, err
+	}
+	cos := make([]float64, len(dot))
+	for i := uint64(0); i < nA; i++ {
+		for j := uint64(0); j < nB; j++ {
+			d, qa, qb := dot[i*nB+j], sumSqA[i], sumSqB[j]
+			switch {
+			case d == math.MaxUint64 || qa == math.MaxUint64 || qb == math.MaxUint64:
+				cos[i*nB+j] = math.NaN()
+			case qa != 0 && qb != 0:
+				cos[i*nB+j] = float64(d) / (math.Sqrt(float64(qa)) * math.Sqrt(float64(qb)))
+			}
+		}
+	}
+	return cos, nil
 }

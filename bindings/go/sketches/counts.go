@@ -98,6 +98,17 @@ func (s *Sets) Totals() ([]uint64, error) {
 	return totals[:nSets], s.eng.err(rc)
 }
 
+// SumSq returns, per set, the sum of its squared counts, saturating at 2^64-1 (bsk_sets_sumsq): the squared norm that
+// (*Compare).Cosine divides by; for sets without counts, their sizes.
+func (s *Sets) SumSq() ([]uint64, error) {
+	var nSets, nValues C.uint64_t
+	C.bsk_sets_info(s.h, &nSets, &nValues)
+	sumsq := make([]uint64, uint64(nSets)+1)
+	rc := C.bsk_sets_sumsq(s.eng.ctx, s.h, 0, nSets, (*C.uint64_t)(unsafe.Pointer(&sumsq[0])))
+	runtime.KeepAlive(s)
+	return sumsq[:nSets], s.eng.err(rc)
+}
+
 // SetsFromHostCounted loads sets with their counts from the host (bsk_sets_from_host_counted): SetsFromHost's rules, and no
 // count may be 0.
 func (e *Engine) SetsFromHostCounted(offsets []uint64, values []uint64, counts []uint32) (*Sets, error) {

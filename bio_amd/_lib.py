@@ -184,6 +184,10 @@ SYMBOLS = [
     ("bsk_compare_fetch", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64]),
     ("bsk_compare_device", C.c_int, [_vp, _pp, _pp]),
     ("bsk_compare_release", None, [_vp]),
+    ("bsk_sets_compare_counted", C.c_int, [_vp, _vp, _vp, C.c_uint64, _pp]),
+    ("bsk_compare_weights_device", C.c_int, [_vp, _pp, _pp]),
+    ("bsk_compare_fetch_weights", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64]),
+    ("bsk_sets_sumsq", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp]),
 ]
 SETS_PER_SEQUENCE, SETS_WHOLE_BATCH = 0, 1
 SETOP_UNION, SETOP_INTERSECT, SETOP_DIFF, SETOP_SYMDIFF = 0, 1, 2, 3

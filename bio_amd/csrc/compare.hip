@@ -19,6 +19,14 @@
 // -- different c, any j -- never meet on a bank, and the two rows of a half at most 2-way.  The staging thread (j, c) = (k * 16 + t / 16,
 // t % 16) writes s_b[k * 256 + t]: consecutive, conflict-free.
 //
+// k_cmp_tile_w (bsk_sets_compare_counted): the tile, round rule and window of k_cmp_tile, with a u32 count window beside every value
+// window -- s_ac[r * CMP_WINDOW + j] and s_bc[j * CMP_COLS + c], the indices of the values -- staged in the loops that stage the values,
+// from the cursors the values use, so a value that is copied again next round brings its count again.  A lane reads two counts only
+// where its two values are equal, at the indices they were read from, and keeps two more sums: the products (u64, saturating) and the
+// minima (u64, exact).  An uncounted operand's count window is filled with ones.  ds_read_b32 banks are (dword mod 32): the lanes of a
+// row read one a-count (broadcast) and the b-counts (j & 1) * 16 + c -- never two lanes of a row on one bank, the two rows of a
+// 32-lane half at most 2-way, as for the values.  k_cmp_tile itself is not touched.
+//
 // bsk_sets_bottom: the sizes min(n, size) through the library's scan, then a gather by groups of lanes (8 per set while the kept sets
 // average at most CMP_BT_SMALL values, else a wavefront per set).
 #include <hip/hip_runtime.h>
@@ -34,6 +42,7 @@
 #define CMP_COLS 16             // b-sets of a tile
 #define CMP_WINDOW 128          // values of a set staged per round: 32 windows x 128 x 8 B = 32 KB of LDS, four workgroups a CU
 #define CMP_BLOCKS_PER_CU 4     // the tile grid's cap
+#define CMP_W_BLOCKS_PER_CU 3   // ... and the weighted tile grid's: its count windows add 16 KB of LDS, three workgroups a CU
 #define CMP_BT_SMALL 16         // bsk_sets_bottom: kept values per set (average) up to which a set takes 8 lanes
 #define CMP_BT_BLOCKS_PER_CU 16 // ... and its gather's cap
 #define CMP_THREADS (CMP_ROWS * CMP_COLS)
@@ -46,6 +55,9 @@ struct bsk_compare {
     size_t c_shared = 0, c_total = 0;         // bytes allocated (grow-only)
     char plan[256] = "";
     u64 figures[3] = {};  // tiles run, rounds summed over the tiles, most rounds of one tile
+    bool weighted = false;                // the last compare into it was bsk_sets_compare_counted: dot and min_sum are valid
+    u64 *dot = nullptr, *msum = nullptr;  // [n_a * n_b] row-major (grow-only, kept by an unweighted compare)
+    size_t c_dot = 0, c_msum = 0;
 };
 
 namespace {
@@ -165,6 +177,135 @@ __global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile(const u64 *aoff, const
     }
 }
 
+// the weighted tile: k_cmp_tile's rounds, with the counts beside the values (ac / bc NULL: an uncounted operand, every count 1)
+__global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile_w(const u64 *aoff, const u64 *av, const u32 *ac, u64 n_a, const u64 *boff, const u64 *bv, const u32 *bc, u64 n_b,
+                                                           u32 lim, u64 ntiles, u64 tiles_x, u32 *shared, u32 *total, u64 *dot, u64 *msum, u64 *fig) {
+    __shared__ u64 s_a[CMP_ROWS * CMP_WINDOW];
+    __shared__ u64 s_b[CMP_COLS * CMP_WINDOW];
+    __shared__ u32 s_ac[CMP_ROWS * CMP_WINDOW];  // the count of s_a[i]
+    __shared__ u32 s_bc[CMP_COLS * CMP_WINDOW];  // the count of s_b[i]
+    __shared__ u64 s_from[CMP_SETS];
+    __shared__ u32 s_n[CMP_SETS];
+    __shared__ u32 s_cnt[CMP_SETS];
+    __shared__ int s_last;
+    const int t = threadIdx.x, r = t / CMP_COLS, c = t % CMP_COLS;
+    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const u64 i0 = (tile / tiles_x) * CMP_ROWS, j0 = (tile % tiles_x) * CMP_COLS;
+        const u64 *vals = t < CMP_ROWS ? av : bv;
+        u64 base = 0;
+        u32 len = 0, start = 0;
+        if (t < CMP_SETS) {
+            const bool isa = t < CMP_ROWS;
+            const u64 g = isa ? i0 + t : j0 + (t - CMP_ROWS);
+            const u64 *off = isa ? aoff : boff;
+            if (g < (isa ? n_a : n_b)) {
+                base = off[g];
+                const u64 sz = off[g + 1] - base;
+                len = sz < (u64)lim ? (u32)sz : lim;
+            }
+        }
+        const bool pair = i0 + r < n_a && j0 + c < n_b;
+        u32 tot = 0, sh = 0, rounds = 0;
+        u64 dt = 0, ms = 0;
+        for (;;) {
+            u64 cand = 0;
+            bool has = false;
+            if (t < CMP_SETS) {
+                const u32 rem = len - start;
+                has = rem > CMP_WINDOW;
+                s_from[t] = base + start;
+                s_n[t] = has ? CMP_WINDOW : rem;
+                if (has) cand = vals[base + start + CMP_WINDOW];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < CMP_ROWS * CMP_WINDOW / CMP_THREADS; ++k) {
+                const int idx = k * CMP_THREADS + t, s = idx / CMP_WINDOW, j = idx % CMP_WINDOW;
+                if ((u32)j < s_n[s]) {
+                    s_a[idx] = av[s_from[s] + j];
+                    s_ac[idx] = ac ? ac[s_from[s] + j] : 1u;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < CMP_WINDOW / CMP_ROWS; ++k) {
+                const int j = k * CMP_ROWS + r;
+                if ((u32)j < s_n[CMP_ROWS + c]) {
+                    s_b[k * CMP_THREADS + t] = bv[s_from[CMP_ROWS + c] + j];
+                    s_bc[k * CMP_THREADS + t] = bc ? bc[s_from[CMP_ROWS + c] + j] : 1u;
+                }
+            }
+            __syncthreads();
+            if (t < 64) {
+                const bool any = __ballot(has) != 0;
+                u64 vhi = has ? cand : ~0ull;
+                for (int d = 32; d; d >>= 1) {
+                    const u64 o = __shfl_xor(vhi, d, 64);
+                    vhi = o < vhi ? o : vhi;
+                }
+                if (t < CMP_SETS) {
+                    u32 cnt = s_n[t];
+                    if (any) {
+                        u32 lo = 0, hi = cnt;
+                        while (lo < hi) {
+                            const u32 mid = (lo + hi) >> 1;
+                            const u64 v = t < CMP_ROWS ? s_a[t * CMP_WINDOW + mid] : s_b[mid * CMP_COLS + (t - CMP_ROWS)];
+                            if (v < vhi) lo = mid + 1;
+                            else hi = mid;
+                        }
+                        cnt = lo;
+                    }
+                    s_cnt[t] = cnt;
+                    start += cnt;
+                }
+                if (t == 0) s_last = any ? 0 : 1;
+            }
+            __syncthreads();
+            ++rounds;
+            if (pair && tot < lim) {
+                const u32 ea = s_cnt[r], eb = s_cnt[CMP_ROWS + c];
+                u32 ia = 0, ib = 0;
+                if (ea && eb) {
+                    u64 x = s_a[r * CMP_WINDOW], y = s_b[c];
+                    for (;;) {
+                        ++tot;
+                        const bool le = x <= y, ge = x >= y;
+                        if (le && ge) {  // both hold it: its counts, from where the two values were read
+                            const u32 ca = s_ac[r * CMP_WINDOW + ia], cb = s_bc[ib * CMP_COLS + c];
+                            const u64 p = (u64)ca * cb;
+                            ++sh;
+                            dt += p;
+                            dt = dt < p ? ~0ull : dt;  // saturating: a wrapped sum is below its last term
+                            ms += ca < cb ? ca : cb;
+                        }
+                        ia += le ? 1u : 0u;
+                        ib += ge ? 1u : 0u;
+                        if (tot >= lim || ia >= ea || ib >= eb) break;
+                        if (le) x = s_a[r * CMP_WINDOW + ia];
+                        if (ge) y = s_b[ib * CMP_COLS + c];
+                    }
+                }
+                // what the other window still holds is in one set only: it adds to the total, to neither sum
+                const u32 rest = (ea - ia) + (eb - ib), room = lim - tot;
+                tot += rest < room ? rest : room;
+            }
+            const int last = s_last;
+            if (!__syncthreads_or(pair && tot < lim) || last) break;
+        }
+        if (pair) {
+            const u64 cell = (i0 + r) * n_b + j0 + c;
+            shared[cell] = sh;
+            total[cell] = tot;
+            dot[cell] = dt;
+            msum[cell] = ms;
+        }
+        if (t == 0) {
+            atomicAdd((unsigned long long *)&fig[0], 1ull);
+            atomicAdd((unsigned long long *)&fig[1], (unsigned long long)rounds);
+            atomicMax((unsigned long long *)&fig[2], (unsigned long long)rounds);
+        }
+    }
+}
+
 // ---- bsk_sets_bottom ----
 struct BtSize {  // what set r keeps
     const u64 *offs;
@@ -246,7 +387,7 @@ int bottom_impl(bsk_ctx *ctx, const bsk_sets *s, u64 n, bsk_sets *res) {
     return BSK_OK;
 }
 
-int compare_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit, bsk_compare *res) {
+int compare_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit, bsk_compare *res, bool weighted) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const u64 n_a = a->n_sets, n_b = b->n_sets, cells = n_a * n_b;
@@ -254,10 +395,16 @@ int compare_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit, 
     res->n_b = n_b;
     res->limit = limit;
     res->figures[0] = res->figures[1] = res->figures[2] = 0;
+    res->weighted = false;  // (an unweighted compare into a weighted object keeps the two arrays, like a counted bsk_sets written by an uncounted entry)
     HIPCHK(ctx, cmp_grow(&res->shared, &res->c_shared, (cells ? cells : 1) * 4));
     HIPCHK(ctx, cmp_grow(&res->total, &res->c_total, (cells ? cells : 1) * 4));
+    if (weighted) {
+        HIPCHK(ctx, cmp_grow(&res->dot, &res->c_dot, (cells ? cells : 1) * 8));
+        HIPCHK(ctx, cmp_grow(&res->msum, &res->c_msum, (cells ? cells : 1) * 8));
+    }
     if (cells == 0) {
-        snprintf(res->plan, sizeof res->plan, "bsk_sets_compare: no pairs");
+        snprintf(res->plan, sizeof res->plan, weighted ? "bsk_sets_compare_counted: no pairs" : "bsk_sets_compare: no pairs");
+        res->weighted = weighted;
         return BSK_OK;
     }
     void *bf = nullptr;
@@ -267,15 +414,22 @@ int compare_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit, 
     const u64 tiles_x = (n_b + CMP_COLS - 1) / CMP_COLS, ntiles = ((n_a + CMP_ROWS - 1) / CMP_ROWS) * tiles_x;
     // the inputs hold fewer than 2^32 values together, so no total reaches 2^32 - 1 before its union ends
     const u32 lim = limit == 0 || limit > 0xffffffffull ? 0xffffffffu : (u32)limit;
-    const unsigned grid = (unsigned)std::min<u64>(ntiles, (u64)ctx->cus * CMP_BLOCKS_PER_CU);
-    hipLaunchKernelGGL(k_cmp_tile, dim3(grid), dim3(CMP_THREADS), 0, st, (const u64 *)a->offsets, (const u64 *)a->values, n_a, (const u64 *)b->offsets, (const u64 *)b->values, n_b,
-                       lim, ntiles, tiles_x, res->shared, res->total, fig);
+    const unsigned grid = (unsigned)std::min<u64>(ntiles, (u64)ctx->cus * (weighted ? CMP_W_BLOCKS_PER_CU : CMP_BLOCKS_PER_CU));
+    if (weighted)
+        hipLaunchKernelGGL(k_cmp_tile_w, dim3(grid), dim3(CMP_THREADS), 0, st, (const u64 *)a->offsets, (const u64 *)a->values, (const u32 *)(a->counted ? a->counts : nullptr), n_a,
+                           (const u64 *)b->offsets, (const u64 *)b->values, (const u32 *)(b->counted ? b->counts : nullptr), n_b, lim, ntiles, tiles_x, res->shared, res->total,
+                           res->dot, res->msum, fig);
+    else
+        hipLaunchKernelGGL(k_cmp_tile, dim3(grid), dim3(CMP_THREADS), 0, st, (const u64 *)a->offsets, (const u64 *)a->values, n_a, (const u64 *)b->offsets, (const u64 *)b->values, n_b,
+                           lim, ntiles, tiles_x, res->shared, res->total, fig);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, fig, 24, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     for (int i = 0; i < 3; ++i) res->figures[i] = ctx->h_pinned[i];
-    snprintf(res->plan, sizeof res->plan, "bsk_sets_compare: k_cmp_tile, %llu x %llu pairs in %llu tiles of %d x %d, windows of %d values, limit %llu", (unsigned long long)n_a,
-             (unsigned long long)n_b, (unsigned long long)ntiles, CMP_ROWS, CMP_COLS, CMP_WINDOW, (unsigned long long)limit);
+    snprintf(res->plan, sizeof res->plan, "%s, %llu x %llu pairs in %llu tiles of %d x %d, windows of %d values, limit %llu",
+             weighted ? "bsk_sets_compare_counted: k_cmp_tile_w" : "bsk_sets_compare: k_cmp_tile", (unsigned long long)n_a, (unsigned long long)n_b, (unsigned long long)ntiles,
+             CMP_ROWS, CMP_COLS, CMP_WINDOW, (unsigned long long)limit);
+    res->weighted = weighted;
     return BSK_OK;
 }
 
@@ -286,6 +440,8 @@ extern "C" void bsk_compare_release(bsk_compare *c) {
     if (c->ctx) (void)hipSetDevice(c->ctx->device);
     (void)hipFree(c->shared);
     (void)hipFree(c->total);
+    (void)hipFree(c->dot);
+    (void)hipFree(c->msum);
     delete c;
 }
 
@@ -308,9 +464,12 @@ extern "C" int bsk_sets_bottom(bsk_ctx *ctx, const bsk_sets *s, uint64_t n, bsk_
     return BSK_OK;
 }
 
-extern "C" int bsk_sets_compare(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, uint64_t limit, bsk_compare **cmp) {
-    if (!ctx || !a || !b || !cmp) return fail_arg(ctx, "bsk_sets_compare: null argument");
-    if (a->ctx != ctx || b->ctx != ctx || (*cmp && (*cmp)->ctx != ctx)) return fail_arg(ctx, "bsk_sets_compare: the sets or the result belong to another context");
+namespace {
+// the checks and the *cmp rules both compares share; `weighted`: bsk_sets_compare_counted
+int compare_entry(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, uint64_t limit, bsk_compare **cmp, bool weighted) {
+    if (!ctx || !a || !b || !cmp) return fail_arg(ctx, weighted ? "bsk_sets_compare_counted: null argument" : "bsk_sets_compare: null argument");
+    if (a->ctx != ctx || b->ctx != ctx || (*cmp && (*cmp)->ctx != ctx))
+        return fail_arg(ctx, weighted ? "bsk_sets_compare_counted: the sets or the result belong to another context" : "bsk_sets_compare: the sets or the result belong to another context");
     bsk_compare *res = *cmp;
     *cmp = nullptr;
     // both limits before anything is allocated (a == b holds its values once)
@@ -319,13 +478,14 @@ extern "C" int bsk_sets_compare(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets 
     const bool many_cells = a->n_sets && b->n_sets > (1ULL << 31) / a->n_sets;
     if (many_values || many_cells) {
         bsk_compare_release(res);
-        ctx->err = many_values ? "bsk_sets_compare: 2^32 values or more (split the sets)" : "bsk_sets_compare: more than 2^31 cells (split the sets)";
+        if (weighted) ctx->err = many_values ? "bsk_sets_compare_counted: 2^32 values or more (split the sets)" : "bsk_sets_compare_counted: more than 2^31 cells (split the sets)";
+        else ctx->err = many_values ? "bsk_sets_compare: 2^32 values or more (split the sets)" : "bsk_sets_compare: more than 2^31 cells (split the sets)";
         return BSK_ERR_UNSUPPORTED;
     }
     if (!res) res = new (std::nothrow) bsk_compare();
     if (!res) return BSK_ERR_NOMEM;
     res->ctx = ctx;
-    const int rc = compare_impl(ctx, a, b, limit, res);
+    const int rc = compare_impl(ctx, a, b, limit, res, weighted);
     if (rc != BSK_OK) {
         bsk_compare_release(res);
         return rc;
@@ -333,6 +493,11 @@ extern "C" int bsk_sets_compare(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets 
     *cmp = res;
     return BSK_OK;
 }
+}  // namespace
+
+extern "C" int bsk_sets_compare(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, uint64_t limit, bsk_compare **cmp) { return compare_entry(ctx, a, b, limit, cmp, false); }
+
+extern "C" int bsk_sets_compare_counted(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, uint64_t limit, bsk_compare **cmp) { return compare_entry(ctx, a, b, limit, cmp, true); }
 
 extern "C" int bsk_compare_info(const bsk_compare *c, uint64_t *n_a, uint64_t *n_b, uint64_t *limit) {
     if (!c) return BSK_ERR_ARG;
@@ -368,5 +533,27 @@ extern "C" int bsk_compare_device(const bsk_compare *c, const uint32_t **shared,
     if (!c) return BSK_ERR_ARG;
     if (shared) *shared = c->shared;
     if (total) *total = c->total;
+    return BSK_OK;
+}
+
+extern "C" int bsk_compare_weights_device(const bsk_compare *c, const uint64_t **dot, const uint64_t **min_sum) {
+    if (!c) return BSK_ERR_ARG;
+    if (dot) *dot = c->weighted ? (const uint64_t *)c->dot : nullptr;
+    if (min_sum) *min_sum = c->weighted ? (const uint64_t *)c->msum : nullptr;
+    return BSK_OK;
+}
+
+extern "C" int bsk_compare_fetch_weights(bsk_ctx *ctx, const bsk_compare *c, uint64_t first_row, uint64_t n_rows, uint64_t *dot, uint64_t *min_sum, uint64_t cell_cap) {
+    if (!ctx || !c) return fail_arg(ctx, "bsk_compare_fetch_weights: null argument");
+    if (c->ctx != ctx) return fail_arg(ctx, "bsk_compare_fetch_weights: the result belongs to another context");
+    if (!c->weighted) return fail_arg(ctx, "bsk_compare_fetch_weights: the result is not weighted (bsk_sets_compare_counted makes one)");
+    if (first_row > c->n_a || n_rows > c->n_a - first_row) return fail_arg(ctx, "bsk_compare_fetch_weights: rows outside the matrix");
+    const u64 cells = n_rows * c->n_b;  // (at most 2^31)
+    if (cells > cell_cap) return fail_arg(ctx, "bsk_compare_fetch_weights: cell_cap too small");
+    if (cells == 0 || (!dot && !min_sum)) return BSK_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (dot) HIPCHK(ctx, hipMemcpyAsync(dot, c->dot + first_row * c->n_b, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (min_sum) HIPCHK(ctx, hipMemcpyAsync(min_sum, c->msum + first_row * c->n_b, cells * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return BSK_OK;
 }

@@ -12,6 +12,8 @@
 //
 // bsk_sets_filter_counts: flags -> the library's scan -> scatter of values and counts -> new offsets, as sets.hip compacts.
 // bsk_sets_totals: one scan of the counts (u64: exact) and a difference at the sets' offsets; no thread walks a set.
+// bsk_sets_sumsq: a group of lanes per set sums c * c with saturating adds and reduces by shuffles (a difference of prefix sums, as
+// bsk_sets_totals takes, cannot saturate correctly: the prefix would have to).
 // The counted set algebra (bsk_sets_op_counted) lives with the merge kernels in setops.hip.
 #include <hip/hip_runtime.h>
 
@@ -132,6 +134,22 @@ __global__ void k_ct_totals(const u64 *offs, const u64 *csum, u64 count, u64 *ou
     for (u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x; s < count; s += (u64)gridDim.x * blockDim.x) {
         const u64 a = offs[s], b = offs[s + 1];
         out[s] = csum ? csum[b] - csum[a] : b - a;
+    }
+}
+// ---- bsk_sets_sumsq: LANES lanes a set; saturating addition of non-negative terms is associative, so any order gives min(sum, 2^64 - 1) ----
+__device__ __forceinline__ u64 add_sat(u64 a, u64 b) {
+    const u64 s = a + b;
+    return s < a ? ~0ull : s;
+}
+template <int LANES>
+__global__ __launch_bounds__(256) void k_ct_sumsq(const u64 *offs, const u32 *c, u64 count, u64 *out) {
+    const u64 lane = threadIdx.x % LANES;
+    for (u64 s = ((u64)blockIdx.x * 256 + threadIdx.x) / LANES; s < count; s += (u64)gridDim.x * (256 / LANES)) {  // (a group enters and leaves together)
+        const u64 a = offs[s], b = offs[s + 1];
+        u64 acc = 0;
+        for (u64 i = a + lane; i < b; i += LANES) acc = add_sat(acc, (u64)c[i] * c[i]);
+        for (int d = LANES / 2; d; d >>= 1) acc = add_sat(acc, __shfl_xor(acc, d, LANES));
+        if (lane == 0) out[s] = acc;
     }
 }
 
@@ -318,6 +336,29 @@ extern "C" int bsk_sets_totals(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, 
     hipLaunchKernelGGL(k_ct_totals, dim3(ct_grid(ctx, count)), dim3(256), 0, st, (const u64 *)(s->offsets + first), (const u64 *)csum, count, static_cast<u64 *>(bo));
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(totals, bo, count * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return BSK_OK;
+}
+
+extern "C" int bsk_sets_sumsq(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t count, uint64_t *sumsq) {
+    if (!ctx || !s || (count && !sumsq)) return fail_arg(ctx, "bsk_sets_sumsq: null argument");
+    if (s->ctx != ctx) return fail_arg(ctx, "bsk_sets_sumsq: the sets belong to another context");
+    if (first > s->n_sets || count > s->n_sets - first) return fail_arg(ctx, "bsk_sets_sumsq: range outside the sets");
+    if (count == 0) return BSK_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    void *bo = nullptr;
+    HIPCHK(ctx, ct_pool(ctx, 44, count * 8, &bo));
+    const u64 *offs = s->offsets + first;
+    if (!s->counted) {  // every count is 1: the sizes
+        hipLaunchKernelGGL(k_ct_totals, dim3(ct_grid(ctx, count)), dim3(256), 0, st, offs, (const u64 *)nullptr, count, static_cast<u64 *>(bo));
+    } else if (s->n_values <= s->n_sets * 16) {  // small sets (16 values on average): 8 lanes a set
+        hipLaunchKernelGGL(k_ct_sumsq<8>, dim3(ct_grid(ctx, count * 8)), dim3(256), 0, st, offs, (const u32 *)s->counts, count, static_cast<u64 *>(bo));
+    } else {  // a wavefront a set
+        hipLaunchKernelGGL(k_ct_sumsq<64>, dim3(ct_grid(ctx, count * 64)), dim3(256), 0, st, offs, (const u32 *)s->counts, count, static_cast<u64 *>(bo));
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(sumsq, bo, count * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     return BSK_OK;
 }

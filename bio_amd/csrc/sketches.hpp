@@ -243,6 +243,15 @@ class DeviceSets : public Owned<bsk_sets, bsk_sets_release> {
         return rc;
     }
 
+    // per set the sum of its squared counts, saturating at 2^64 - 1 (the sets' sizes for sets without counts): the norms of cosine
+    int sumsq(Engine &e, std::vector<uint64_t> &out) const {
+        const uint64_t n = n_sets();
+        out.assign(n + 1, 0);
+        const int rc = bsk_sets_sumsq(e.ctx(), p_, 0, n, out.data());
+        out.resize(n);
+        return rc;
+    }
+
     // ---- MinHash: every set of s cut to its min(n, size) smallest values (counts ride along) INTO this object, as op() ----
     int bottom(Engine &e, const DeviceSets &s, uint64_t n) { return bsk_sets_bottom(e.ctx(), s.get(), n, &p_); }
 };
@@ -253,6 +262,24 @@ class SetsCompare : public Owned<bsk_compare, bsk_compare_release> {
     // every set of a against every set of b INTO this object (empty, or the result of an earlier compare on this engine: arrays kept,
     // grow only); limit: the distinct values of a pair's union that are walked (0: all -- the exact Jaccard; n: the Mash estimator)
     int compare(Engine &e, const DeviceSets &a, const DeviceSets &b, uint64_t limit = 0) { return bsk_sets_compare(e.ctx(), a.get(), b.get(), limit, &p_); }
+    // compare() with the counts: besides shared and total, dot = the sum of ca * cb (saturating at 2^64 - 1) and min_sum = the sum of min(ca, cb)
+    // over the walked values both sets hold; sets without counts count 1 for every value.  A later compare() leaves the object unweighted
+    int compare_counted(Engine &e, const DeviceSets &a, const DeviceSets &b, uint64_t limit = 0) { return bsk_sets_compare_counted(e.ctx(), a.get(), b.get(), limit, &p_); }
+    bool weighted() const {
+        const uint64_t *d = nullptr, *m = nullptr;
+        return bsk_compare_weights_device(p_, &d, &m) == BSK_OK && d != nullptr && m != nullptr;
+    }
+    int fetch_weights(Engine &e, std::vector<uint64_t> &dot, std::vector<uint64_t> &min_sum) const {  // BSK_ERR_ARG for an unweighted result
+        uint64_t n_a = 0, n_b = 0;
+        int rc = bsk_compare_info(p_, &n_a, &n_b, nullptr);
+        if (rc != BSK_OK) return rc;
+        dot.assign(n_a * n_b + 1, 0);
+        min_sum.assign(n_a * n_b + 1, 0);
+        rc = bsk_compare_fetch_weights(e.ctx(), p_, 0, n_a, dot.data(), min_sum.data(), n_a * n_b);
+        dot.resize(n_a * n_b);
+        min_sum.resize(n_a * n_b);
+        return rc;
+    }
     int info(uint64_t &n_a, uint64_t &n_b, uint64_t &limit) const { return bsk_compare_info(p_, &n_a, &n_b, &limit); }
     // figures: tiles run, rounds summed over the tiles, most rounds of one tile
     const char *plan(uint64_t figures[3]) const {

@@ -379,6 +379,14 @@ class Sets:
         self.eng._chk(self.eng.lib.bsk_sets_totals(self.eng.ctx, self.h, 0, ns, t.ctypes.data))
         return t[:ns]
 
+    def sumsq(self) -> np.ndarray:
+        """per set the sum of its squared counts, u64, saturating at 2^64 - 1 (bsk_sets_sumsq): the squared norm of the abundance
+        vector; the sets' sizes for sets without counts"""
+        ns = self.info()["n_sets"]
+        t = np.zeros(max(ns, 1), np.uint64)
+        self.eng._chk(self.eng.lib.bsk_sets_sumsq(self.eng.ctx, self.h, 0, ns, t.ctypes.data))
+        return t[:ns]
+
     # -- MinHash (bsk_sets_bottom / bsk_sets_compare)
     def bottom(self, n: int, into: Optional["Sets"] = None) -> "Sets":
         """Every set cut to its min(n, size) smallest values, counts included when the sets are counted (bsk_sets_bottom): the
@@ -397,6 +405,20 @@ class Sets:
         self.eng._chk(rc)
         res = reuse if reuse is not None else Compare(self.eng)
         res._bind(h, np.diff(self.offsets()))
+        return res
+
+    def compare_counted(self, other: Optional["Sets"] = None, limit: int = 0, reuse: Optional["Compare"] = None) -> "Compare":
+        """compare() with the counts (bsk_sets_compare_counted): shared and total as compare() gives them, and over the walked values
+        both sets hold dot = the sum of the products of the two counts (u64, saturating) and min_sum = the sum of their minima.
+        Sets without counts count 1 for every value.  The Compare keeps both operands for its norms (cosine() and its kin)."""
+        other = self if other is None else other
+        h = reuse.h if reuse is not None and reuse.h else C.c_void_p()
+        rc = self.eng.lib.bsk_sets_compare_counted(self.eng.ctx, self.h, other.h, limit, C.byref(h))
+        if reuse is not None:
+            reuse.h = h if h.value else None  # (kept on an argument error, released by the library on any other)
+        self.eng._chk(rc)
+        res = reuse if reuse is not None else Compare(self.eng)
+        res._bind(h, np.diff(self.offsets()), (self, other))
         return res
 
     def plan(self):
@@ -419,15 +441,19 @@ class Sets:
 
 
 class Compare:
-    """Dense all-pairs comparison (bsk_compare): shared[n_a, n_b] and total[n_a, n_b] (u32), fetched on first use."""
+    """Dense all-pairs comparison (bsk_compare): shared[n_a, n_b] and total[n_a, n_b] (u32), fetched on first use; after
+    Sets.compare_counted also dot[n_a, n_b] and min_sum[n_a, n_b] (u64)."""
+
+    _whost = _norms = _operands = None  # the weighted side: (dot, min_sum); (sumsq_a, sumsq_b, totals_a, totals_b); the two Sets
 
     def __init__(self, eng: "Engine"):
         self.eng, self.h = eng, None
         self._host = None
 
-    def _bind(self, h, a_sizes: np.ndarray):
+    def _bind(self, h, a_sizes: np.ndarray, operands=None):
         self.h, self._host = h, None
         self.a_sizes = a_sizes.astype(np.uint64)
+        self._whost, self._norms, self._operands = None, None, operands
 
     def info(self):
         na, nb, lim = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -489,6 +515,82 @@ class Compare:
         nz = j > 0
         d[nz] = np.maximum(0.0, -np.log(2.0 * j[nz] / (1.0 + j[nz])) / k)
         return d
+
+    # -- the weighted side (bsk_sets_compare_counted)
+    @property
+    def weighted(self) -> bool:
+        """whether the last compare into this object kept dot and min_sum (bsk_compare_weights_device gives arrays)"""
+        if not self.h:
+            return self._whost is not None
+        pd, pm = C.c_void_p(), C.c_void_p()
+        self.eng._chk(self.eng.lib.bsk_compare_weights_device(self.h, C.byref(pd), C.byref(pm)))
+        return bool(pd.value) and bool(pm.value)
+
+    def fetch_weights(self, first_row: int = 0, n_rows: Optional[int] = None):
+        """bsk_compare_fetch_weights -> (dot[n_rows, n_b], min_sum[n_rows, n_b]) u64; an unweighted result raises"""
+        inf = self.info()
+        if n_rows is None:
+            n_rows = inf["n_a"] - first_row
+        cells = max(n_rows, 0) * inf["n_b"]
+        dt, ms = np.zeros(max(cells, 1), np.uint64), np.zeros(max(cells, 1), np.uint64)
+        self.eng._chk(self.eng.lib.bsk_compare_fetch_weights(self.eng.ctx, self.h, first_row, n_rows, dt.ctypes.data, ms.ctypes.data, cells))
+        return dt[:cells].reshape(n_rows, inf["n_b"]), ms[:cells].reshape(n_rows, inf["n_b"])
+
+    def _wcache(self):
+        if self._whost is None:
+            if not self.weighted:
+                raise ValueError("not a weighted result: use Sets.compare_counted")
+            self._whost = self.fetch_weights()
+        return self._whost
+
+    @property
+    def dot(self) -> np.ndarray:
+        return self._wcache()[0]
+
+    @property
+    def min_sum(self) -> np.ndarray:
+        return self._wcache()[1]
+
+    def _whole(self, what: str):
+        """(dot, min_sum, sumsq_a, sumsq_b, totals_a, totals_b) of a weighted result over whole sets"""
+        dt, ms = self._wcache()
+        if self.info()["limit"] != 0:
+            raise ValueError(what + " is defined on whole sets: compare_counted with limit=0")
+        if self._norms is None:
+            a, b = self._operands
+            qa, ta = a.sumsq(), a.totals()
+            qb, tb = (qa, ta) if b is a else (b.sumsq(), b.totals())
+            self._norms = (qa, qb, ta, tb)
+        return (dt, ms) + tuple(self._norms)
+
+    def cosine(self) -> np.ndarray:
+        """dot / (sqrt(sumsq_a[i]) * sqrt(sumsq_b[j])) as float64: 0.0 where a norm is 0, NaN where dot or either norm is saturated"""
+        dt, _, qa, qb, _, _ = self._whole("cosine")
+        top = int(np.iinfo(np.uint64).max)
+        den = np.sqrt(qa.astype(np.float64))[:, None] * np.sqrt(qb.astype(np.float64))[None, :]
+        cos = np.divide(dt.astype(np.float64), den, out=np.zeros(dt.shape, np.float64), where=den != 0)
+        cos[(dt == top) | (qa == top)[:, None] | (qb == top)[None, :]] = np.nan
+        return cos
+
+    def angular_similarity(self) -> np.ndarray:
+        """1 - 2 acos(min(cosine, 1)) / pi: what sourmash compare reports for signatures with abundance"""
+        return 1.0 - 2.0 * np.arccos(np.minimum(self.cosine(), 1.0)) / np.pi
+
+    def weighted_jaccard(self) -> np.ndarray:
+        """min_sum / (totals_a[i] + totals_b[j] - min_sum) -- the sum of minima over the sum of maxima -- 0.0 where that is 0"""
+        _, ms, _, _, ta, tb = self._whole("weighted_jaccard")
+        m = ms.astype(np.float64)
+        den = ta.astype(np.float64)[:, None] + tb.astype(np.float64)[None, :] - m
+        return np.divide(m, den, out=np.zeros_like(m), where=den != 0)
+
+    def bray_curtis(self) -> np.ndarray:
+        """1 - 2 min_sum / (totals_a[i] + totals_b[j]) (the dissimilarity), 0.0 where the denominator is 0"""
+        _, ms, _, _, ta, tb = self._whole("bray_curtis")
+        m = ms.astype(np.float64)
+        den = ta.astype(np.float64)[:, None] + tb.astype(np.float64)[None, :]
+        out, nz = np.zeros_like(m), den != 0
+        out[nz] = 1.0 - 2.0 * m[nz] / den[nz]
+        return out
 
     def close(self):
         if self.h:

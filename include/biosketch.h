@@ -669,6 +669,34 @@ int bsk_compare_fetch(bsk_ctx *ctx, const bsk_compare *c, uint64_t first_row, ui
 int bsk_compare_device(const bsk_compare *c, const uint32_t **shared, const uint32_t **total);
 void bsk_compare_release(bsk_compare *c);
 
+/* ---- abundance-weighted all-pairs comparison of counted sets ----
+ * bsk_sets_compare_counted walks every pair exactly as bsk_sets_compare does -- the first `limit` distinct values of a[i] | b[j],
+ * ascending (limit == 0: all of them) -- so shared and total are, cell for cell, what bsk_sets_compare gives on the same operands and
+ * limit.  Over the walked values v that BOTH sets hold, with ca(v) and cb(v) their counts, it also keeps two dense row-major u64
+ * matrices on the device:
+ *   dot[i * n_b + j]     = sum of ca(v) * cb(v), saturating at 2^64-1 (one product of two u32 always fits, the sum need not; saturating
+ *                          addition of non-negative terms is associative, so the cell is min(true sum, 2^64-1) whatever the order);
+ *   min_sum[i * n_b + j] = sum of min(ca(v), cb(v)), exact (fewer than 2^32 values of counts below 2^32 cannot overflow).
+ * A value that only one of the sets holds contributes to neither.  An uncounted operand counts 1 for every value, as in
+ * bsk_sets_op_counted; with both operands uncounted dot == min_sum == shared.  Operand limits (2^32 values together, 2^31 cells,
+ * checked before anything is allocated), a == b, empty operands, and the *cmp and error rules are those of bsk_sets_compare.
+ * Re-use: *cmp may be the object of either compare.  The object remembers which one wrote it last: a bsk_sets_compare into a weighted
+ * object leaves it unweighted and keeps the two arrays (as a counted bsk_sets written by an uncounted entry).
+ * bsk_compare_info / _plan / _fetch / _device work unchanged on a weighted result; the plan names the kernel (k_cmp_tile_w) and its
+ * window.  bsk_compare_weights_device: both NULL for an unweighted result.  bsk_compare_fetch_weights: row-range, cap and
+ * foreign-context rules of bsk_compare_fetch; BSK_ERR_ARG for an unweighted result.
+ * What the numbers are for (limit == 0), with bsk_sets_sumsq and bsk_sets_totals of the operands:
+ *   cosine            dot / (sqrt(sumsq(a)[i]) * sqrt(sumsq(b)[j]))       (sourmash compare's angular similarity is 1 - 2 acos(cosine) / pi)
+ *   sum of max        totals(a)[i] + totals(b)[j] - min_sum               (no third matrix is kept)
+ *   weighted Jaccard  min_sum / sum of max;   Bray-Curtis dissimilarity  1 - 2 min_sum / (totals(a)[i] + totals(b)[j])
+ * bsk_sets_sumsq: per set of the range the sum of its squared counts (the squared norm of the abundance vector), saturating at 2^64-1;
+ * an uncounted object gives the sets' sizes; range rules of bsk_sets_totals. */
+int bsk_sets_compare_counted(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, uint64_t limit, bsk_compare **cmp);
+int bsk_compare_weights_device(const bsk_compare *c, const uint64_t **dot, const uint64_t **min_sum);   /* either may be NULL */
+int bsk_compare_fetch_weights(bsk_ctx *ctx, const bsk_compare *c, uint64_t first_row, uint64_t n_rows,
+                              uint64_t *dot, uint64_t *min_sum, uint64_t cell_cap);                       /* either array may be NULL */
+int bsk_sets_sumsq(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t count, uint64_t *sumsq /* host */);
+
 #ifdef __cplusplus
 }
 #endif
