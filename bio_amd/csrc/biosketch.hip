@@ -925,22 +925,9 @@ extern "C" int bsk_result_fetch(bsk_ctx *ctx, const bsk_result *r, uint64_t firs
     // pack on the device (the tuple arrays are slab-organised), then one D2H copy per array
     u64 *d_off = nullptr, *d_h = nullptr;
     u32 *d_p = nullptr;
-    auto fpool = [&](int slot, size_t bytes, void **out) -> hipError_t {
-        if (ctx->tmp_cap[slot] < bytes) {
-            (void)hipFree(ctx->tmp[slot]);
-            ctx->tmp[slot] = nullptr;
-            ctx->tmp_cap[slot] = 0;
-            const size_t want = bytes + bytes / 4 + 256;
-            const hipError_t e2 = hipMalloc(&ctx->tmp[slot], want);
-            if (e2 != hipSuccess) return e2;
-            ctx->tmp_cap[slot] = want;
-        }
-        *out = ctx->tmp[slot];
-        return hipSuccess;
-    };
-    hipError_t e = fpool(12, count * 8, (void **)&d_off);
-    if (e == hipSuccess && hash) e = fpool(13, T * 8, (void **)&d_h);
-    if (e == hipSuccess && pos) e = fpool(14, T * 4, (void **)&d_p);
+    hipError_t e = ctx_pool(ctx, SLOT_FETCH_OFFS, count * 8, &d_off);
+    if (e == hipSuccess && hash) e = ctx_pool(ctx, SLOT_FETCH_HASH, T * 8, &d_h);
+    if (e == hipSuccess && pos) e = ctx_pool(ctx, SLOT_FETCH_POS, T * 4, &d_p);
     for (u64 i = 0; i < count; ++i) refs[i] = offsets[i];  // the pinned buffer carries the offsets back up
     if (e == hipSuccess) e = hipMemcpyAsync(d_off, refs, count * 8, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {

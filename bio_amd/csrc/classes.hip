@@ -193,19 +193,6 @@ bool class_decide(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, int cir
 
 // lists, views and sub-batches of the classes (device passes on the context's stream; the arrays live in the context's pool)
 int class_build(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, const std::vector<ClassCut> &cuts, int bulk, ClassSet *cs) {
-    auto pool = [&](int slot, size_t bytes, void **outp) -> hipError_t {
-        if (ctx->tmp_cap[slot] < bytes) {
-            (void)hipFree(ctx->tmp[slot]);
-            ctx->tmp[slot] = nullptr;
-            ctx->tmp_cap[slot] = 0;
-            const size_t want = bytes + bytes / 4 + 256;
-            const hipError_t e = hipMalloc(&ctx->tmp[slot], want);
-            if (e != hipSuccess) return e;
-            ctx->tmp_cap[slot] = want;
-        }
-        *outp = ctx->tmp[slot];
-        return hipSuccess;
-    };
     u64 n_out = 0;
     for (size_t i = 0; i < cuts.size(); ++i)
         if ((int)i != bulk) n_out += cuts[i].n;
@@ -220,9 +207,9 @@ int class_build(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, const std
     }
     u32 *lists = nullptr;
     u64 *view = nullptr, *sdesc = nullptr;
-    HIPCHK(ctx, pool(21, (n_out + 64) * 4, (void **)&lists));
-    if (!masked) HIPCHK(ctx, pool(22, (b->n + 1024 + 64) * 8, (void **)&view));  // (+ a ticket: k_class_cut writes whole tickets)
-    HIPCHK(ctx, pool(23, (n_out + 64) * 8, (void **)&sdesc));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_CLASS_LISTS, (n_out + 64) * 4, &lists));
+    if (!masked) HIPCHK(ctx, ctx_pool(ctx, SLOT_CLASS_VIEW, (b->n + 1024 + 64) * 8, &view));  // (+ a ticket: k_class_cut writes whole tickets)
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_CLASS_DESC, (n_out + 64) * 8, &sdesc));
     const u32 nblocks = (u32)((b->n + 1023) / 1024);  // k_class_list: a ticket is 16 rows of 64 reads
     int rc = ensure_scratch(ctx, nblocks, 0);
     if (rc != BSK_OK) return rc;

@@ -327,31 +327,6 @@ __global__ __launch_bounds__(256) void k_bt_gather(const u64 *ioff, const u64 *i
     }
 }
 
-hipError_t cmp_pool(bsk_ctx *ctx, int slot, size_t bytes, void **out) {  // slots 45-46: the context's grow-only temporaries of this file
-    if (ctx->tmp_cap[slot] < bytes || !ctx->tmp[slot]) {
-        (void)hipFree(ctx->tmp[slot]);
-        ctx->tmp[slot] = nullptr;
-        ctx->tmp_cap[slot] = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(&ctx->tmp[slot], want);
-        if (e != hipSuccess) return e;
-        ctx->tmp_cap[slot] = want;
-    }
-    *out = ctx->tmp[slot];
-    return hipSuccess;
-}
-template <class T>
-hipError_t cmp_grow(T **p, size_t *cap, size_t bytes) {  // an object's own arrays: grow-only
-    if (*cap >= bytes && *p) return hipSuccess;
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = bytes + bytes / 4 + 256;
-    const hipError_t e = hipMalloc(p, want);
-    if (e == hipSuccess) *cap = want;
-    return e;
-}
-
 int bottom_impl(bsk_ctx *ctx, const bsk_sets *s, u64 n, bsk_sets *res) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -361,22 +336,22 @@ int bottom_impl(bsk_ctx *ctx, const bsk_sets *s, u64 n, bsk_sets *res) {
     res->counted = false;
     res->plan[0] = 0;
     res->by_path[0] = res->by_path[1] = res->by_path[2] = 0;
-    HIPCHK(ctx, cmp_grow(&res->offsets, &res->c_offsets, (G + 1) * 8));
+    HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (G + 1) * 8));
     void *bq = nullptr;
-    HIPCHK(ctx, cmp_pool(ctx, 46, ((G + SCAN_CHUNK - 1) / SCAN_CHUNK + 2 + 8) * 8, &bq));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_BOTTOM_SCAN, (scan_parts(G) + 8) * 8, &bq));
     u64 *tot = static_cast<u64 *>(bq), *part = tot + 8;
     HIPCHK(ctx, hipMemsetAsync(tot, 0, 64, st));
     HIPCHK(ctx, scan_counts(st, BtSize{s->offsets, n}, G, part, res->offsets, tot, (u64 *)nullptr));
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     const u64 M = ctx->h_pinned[0];
-    HIPCHK(ctx, cmp_grow(&res->values, &res->c_values, (M ? M : 1) * 8));
+    HIPCHK(ctx, grow_array(&res->values, &res->c_values, (M ? M : 1) * 8));
     if (s->counted) HIPCHK(ctx, sets_grow_counts(res, M ? M : 1, true));
     if (M) {
         const u32 *ic = s->counted ? s->counts : nullptr;
         const bool small = M <= G * CMP_BT_SMALL;
         const u64 per_block = small ? 256 / 8 : 256 / 64;
-        const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>((G + per_block - 1) / per_block, (u64)ctx->cus * CMP_BT_BLOCKS_PER_CU));
+        const unsigned grid = grid_for(ctx, G, per_block, CMP_BT_BLOCKS_PER_CU);
         if (small) hipLaunchKernelGGL(k_bt_gather<8>, dim3(grid), dim3(256), 0, st, s->offsets, s->values, ic, res->offsets, G, res->values, res->counts);
         else hipLaunchKernelGGL(k_bt_gather<64>, dim3(grid), dim3(256), 0, st, s->offsets, s->values, ic, res->offsets, G, res->values, res->counts);
         HIPCHK(ctx, hipGetLastError());
@@ -396,11 +371,11 @@ int compare_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit, 
     res->limit = limit;
     res->figures[0] = res->figures[1] = res->figures[2] = 0;
     res->weighted = false;  // (an unweighted compare into a weighted object keeps the two arrays, like a counted bsk_sets written by an uncounted entry)
-    HIPCHK(ctx, cmp_grow(&res->shared, &res->c_shared, (cells ? cells : 1) * 4));
-    HIPCHK(ctx, cmp_grow(&res->total, &res->c_total, (cells ? cells : 1) * 4));
+    HIPCHK(ctx, grow_array(&res->shared, &res->c_shared, (cells ? cells : 1) * 4));
+    HIPCHK(ctx, grow_array(&res->total, &res->c_total, (cells ? cells : 1) * 4));
     if (weighted) {
-        HIPCHK(ctx, cmp_grow(&res->dot, &res->c_dot, (cells ? cells : 1) * 8));
-        HIPCHK(ctx, cmp_grow(&res->msum, &res->c_msum, (cells ? cells : 1) * 8));
+        HIPCHK(ctx, grow_array(&res->dot, &res->c_dot, (cells ? cells : 1) * 8));
+        HIPCHK(ctx, grow_array(&res->msum, &res->c_msum, (cells ? cells : 1) * 8));
     }
     if (cells == 0) {
         snprintf(res->plan, sizeof res->plan, weighted ? "bsk_sets_compare_counted: no pairs" : "bsk_sets_compare: no pairs");
@@ -408,7 +383,7 @@ int compare_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit, 
         return BSK_OK;
     }
     void *bf = nullptr;
-    HIPCHK(ctx, cmp_pool(ctx, 45, 64, &bf));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_COMPARE_FIGURES, 64, &bf));
     u64 *fig = static_cast<u64 *>(bf);
     HIPCHK(ctx, hipMemsetAsync(fig, 0, 64, st));
     const u64 tiles_x = (n_b + CMP_COLS - 1) / CMP_COLS, ntiles = ((n_a + CMP_ROWS - 1) / CMP_ROWS) * tiles_x;

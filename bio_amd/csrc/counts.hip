@@ -153,31 +153,7 @@ __global__ __launch_bounds__(256) void k_ct_sumsq(const u64 *offs, const u32 *c,
     }
 }
 
-unsigned ct_grid(const bsk_ctx *ctx, u64 items) { return (unsigned)std::max<u64>(1, std::min<u64>((items + 255) / 256, (u64)ctx->cus * 16)); }
-hipError_t ct_pool(bsk_ctx *ctx, int slot, size_t bytes, void **out) {  // slots 40-44: the context's grow-only temporaries of this file
-    if (ctx->tmp_cap[slot] < bytes || !ctx->tmp[slot]) {
-        (void)hipFree(ctx->tmp[slot]);
-        ctx->tmp[slot] = nullptr;
-        ctx->tmp_cap[slot] = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(&ctx->tmp[slot], want);
-        if (e != hipSuccess) return e;
-        ctx->tmp_cap[slot] = want;
-    }
-    *out = ctx->tmp[slot];
-    return hipSuccess;
-}
-hipError_t ct_grow(u64 **p, size_t *cap, size_t bytes) {
-    if (*cap >= bytes && *p) return hipSuccess;
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = bytes + bytes / 4 + 256;
-    const hipError_t e = hipMalloc(p, want);
-    if (e == hipSuccess) *cap = want;
-    return e;
-}
-u64 ct_parts(u64 n) { return (n + SCAN_CHUNK - 1) / SCAN_CHUNK + 2; }
+unsigned ct_grid(const bsk_ctx *ctx, u64 items) { return grid_for(ctx, items, 256, 16); }
 
 int filter_impl(bsk_ctx *ctx, const bsk_sets *s, u32 lo, u32 hi, bsk_sets *res) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -188,9 +164,9 @@ int filter_impl(bsk_ctx *ctx, const bsk_sets *s, u32 lo, u32 hi, bsk_sets *res) 
     res->counted = false;
     res->by_path[0] = res->by_path[1] = res->by_path[2] = 0;
     snprintf(res->plan, sizeof res->plan, "bsk_sets_filter_counts: %u <= count <= %u", lo, hi);
-    HIPCHK(ctx, ct_grow(&res->offsets, &res->c_offsets, (G + 1) * 8));
+    HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (G + 1) * 8));
     if (N == 0) {
-        HIPCHK(ctx, ct_grow(&res->values, &res->c_values, 8));
+        HIPCHK(ctx, grow_array(&res->values, &res->c_values, 8));
         HIPCHK(ctx, sets_grow_counts(res, 1, true));
         HIPCHK(ctx, hipMemsetAsync(res->offsets, 0, (G + 1) * 8, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
@@ -198,9 +174,9 @@ int filter_impl(bsk_ctx *ctx, const bsk_sets *s, u32 lo, u32 hi, bsk_sets *res) 
         return BSK_OK;
     }
     void *bk = nullptr, *bp = nullptr, *bq = nullptr;
-    HIPCHK(ctx, ct_pool(ctx, 41, N * 4, &bk));
-    HIPCHK(ctx, ct_pool(ctx, 42, (N + 1) * 8, &bp));
-    HIPCHK(ctx, ct_pool(ctx, 43, (ct_parts(N) + 8) * 8, &bq));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_COUNT_KEEP, N * 4, &bk));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_COUNT_POS, (N + 1) * 8, &bp));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_COUNT_SCAN, (scan_parts(N) + 8) * 8, &bq));
     u32 *keep = static_cast<u32 *>(bk);
     u64 *pos = static_cast<u64 *>(bp), *tot = static_cast<u64 *>(bq), *part = tot + 8;
     HIPCHK(ctx, hipMemsetAsync(tot, 0, 64, st));
@@ -210,7 +186,7 @@ int filter_impl(bsk_ctx *ctx, const bsk_sets *s, u32 lo, u32 hi, bsk_sets *res) 
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     const u64 M = ctx->h_pinned[0];
-    HIPCHK(ctx, ct_grow(&res->values, &res->c_values, (M ? M : 1) * 8));
+    HIPCHK(ctx, grow_array(&res->values, &res->c_values, (M ? M : 1) * 8));
     HIPCHK(ctx, sets_grow_counts(res, M ? M : 1, true));
     if (M) hipLaunchKernelGGL(k_fc_scatter, dim3(ct_grid(ctx, N)), dim3(256), 0, st, s->values, s->counts, keep, pos, N, res->values, res->counts);
     hipLaunchKernelGGL(k_fc_offsets, dim3(ct_grid(ctx, G + 1)), dim3(256), 0, st, s->offsets, pos, G, N, M, res->offsets);
@@ -222,18 +198,6 @@ int filter_impl(bsk_ctx *ctx, const bsk_sets *s, u32 lo, u32 hi, bsk_sets *res) 
 }
 
 }  // namespace
-
-hipError_t sets_grow_counts(bsk_sets *s, u64 n, bool slack) {
-    const size_t bytes = (n ? n : 1) * 4;
-    if (s->c_counts >= bytes && s->counts) return hipSuccess;
-    (void)hipFree(s->counts);
-    s->counts = nullptr;
-    s->c_counts = 0;
-    const size_t want = slack ? bytes + bytes / 4 + 256 : bytes;
-    const hipError_t e = hipMalloc(&s->counts, want);
-    if (e == hipSuccess) s->c_counts = want;
-    return e;
-}
 
 u64 sets_run_counts_parts(u64 n) { return n / CNT_CHUNK + 2; }
 
@@ -324,11 +288,11 @@ extern "C" int bsk_sets_totals(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, 
     hipStream_t st = ctx->stream;
     const u64 N = s->n_values;
     void *bo = nullptr, *bp = nullptr, *bq = nullptr;
-    HIPCHK(ctx, ct_pool(ctx, 44, count * 8, &bo));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_COUNT_OUT, count * 8, &bo));
     u64 *csum = nullptr;
     if (s->counted) {
-        HIPCHK(ctx, ct_pool(ctx, 42, (N + 1) * 8, &bp));
-        HIPCHK(ctx, ct_pool(ctx, 43, (ct_parts(N) + 8) * 8, &bq));
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_COUNT_POS, (N + 1) * 8, &bp));
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_COUNT_SCAN, (scan_parts(N) + 8) * 8, &bq));
         csum = static_cast<u64 *>(bp);
         u64 *tot = static_cast<u64 *>(bq);
         HIPCHK(ctx, scan_counts(st, KeepOf{s->counts}, N, tot + 8, csum, tot, (u64 *)nullptr));
@@ -348,7 +312,7 @@ extern "C" int bsk_sets_sumsq(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, u
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     void *bo = nullptr;
-    HIPCHK(ctx, ct_pool(ctx, 44, count * 8, &bo));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_COUNT_OUT, count * 8, &bo));
     const u64 *offs = s->offsets + first;
     if (!s->counted) {  // every count is 1: the sizes
         hipLaunchKernelGGL(k_ct_totals, dim3(ct_grid(ctx, count)), dim3(256), 0, st, offs, (const u64 *)nullptr, count, static_cast<u64 *>(bo));

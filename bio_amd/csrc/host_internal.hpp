@@ -117,7 +117,6 @@ void spare_register(bsk_ctx *ctx, bool add);
 void spare_flush(bsk_ctx *ctx);
 void spare_give(bsk_ctx *ctx, void *p);
 hipError_t spare_take(bsk_ctx *ctx, void **out, size_t bytes);
-int grid_for(bsk_ctx *ctx, u64 items, int block);
 u64 pad_words(u32 maxlen);
 u32 env_u32(const char *name, u32 dflt);
 u32 min_tile_min(const bsk_ctx *ctx);

@@ -30,6 +30,40 @@ struct BskOpts {
     void load();  // biosketch.hip
 };
 
+// The slots of the context's grow-only pool (bsk_ctx::tmp, taken through ctx_pool below).  A buffer lives from its first use to the end of
+// the context; an entry that shares a slot with another says so here.  A new feature takes the free numbers (38, 39, 47) or adds its own
+// before POOL_SLOTS.
+enum PoolSlot {
+    // 0-9 serve two users, each under its own names: a tiled call (tiles.hip) ...
+    SLOT_TILE_START = 0, SLOT_TILE_DESC = 1, SLOT_TILE_ADESC = 2, SLOT_TILE_SEQ = 3, SLOT_TILE_SHIFT = 4, SLOT_TILE_KEEP = 5, SLOT_TILE_FLAGS = 6, SLOT_TILE_SEQ_FLAGS = 7,
+    SLOT_TILE_SEQ_BAD = 8, SLOT_TILE_EXCL = 9,
+    // ... and sets_build (sets.hip); SLOT_SETS_TMP is the sort's temporary storage, then the parts of the scan behind it
+    SLOT_SETS_OFFS = 0, SLOT_SETS_PART = 1, SLOT_SETS_VALUES = 2, SLOT_SETS_UCOUNT = 3, SLOT_SETS_SORTED = 5, SLOT_SETS_HEAD = 6, SLOT_SETS_KEEP = 7, SLOT_SETS_POS = 8,
+    SLOT_SETS_TMP = 9,
+    // the containment search and bsk_hits_top, which runs when the search's temporaries are dead (search.hip)
+    SLOT_SEARCH_QUERY = 10, SLOT_SEARCH_RANGES = 11, SLOT_SEARCH_STAGE = 15, SLOT_SEARCH_LARGE = 30, SLOT_SEARCH_SORT_TMP = 31,
+    // bsk_result_fetch (biosketch.hip) AND bsk_result_fetch_narrow (sets.hip): the packed offsets, hashes and positions of one fetch
+    SLOT_FETCH_OFFS = 12, SLOT_FETCH_HASH = 13, SLOT_FETCH_POS = 14,
+    // bsk_result_compact (sets.hip): the arrays it hands to its caller
+    SLOT_COMPACT_OFFS = 16,
+    SLOT_SCAN_PART = 17,  // bsk_result_compact AND bsk_result_fetch_narrow: the parts of their offset scans (scratch, dead when either returns)
+    SLOT_COMPACT_HASH = 18, SLOT_COMPACT_POS = 19,
+    SLOT_NARROW_OFFS = 20,  // bsk_sets_fetch_narrow AND hits_fetch_narrow: u32 offsets between two synchronisations of the stream
+    // class plans (classes.hip): the parts' lists of reads, the bulk's view, the parts' descriptors -- bsk_ctx::cls_owner says whose
+    SLOT_CLASS_LISTS = 21, SLOT_CLASS_VIEW = 22, SLOT_CLASS_DESC = 23,
+    // two-pass syncmers (launch.hip, make EXPERIMENTS=1)
+    SLOT_SEL_MASK = 24, SLOT_SEL_CNT = 25, SLOT_SEL_UTOT = 26, SLOT_SEL_UBASE = 27,
+    // the ASCII side launch's own reference words and status bytes (launch.hip)
+    SLOT_SIDE_REFS = 28, SLOT_SIDE_STATUS = 29,
+    // set operations (setops.hip): bsk_sets_op's pairs and tiles; bsk_sets_reduce's groups, sorted values, flags and sort storage
+    SLOT_OP_PAIRS = 32, SLOT_OP_TILES = 33, SLOT_REDUCE_GROUPS = 34, SLOT_REDUCE_SORTED = 35, SLOT_REDUCE_VALUES = 36, SLOT_REDUCE_SORT_TMP = 37,
+    // counted sets: sets_build's run lengths (sets.hip); the filter's flags; positions or count sums, and the scan behind them; the totals (counts.hip)
+    SLOT_COUNT_RUNS = 40, SLOT_COUNT_KEEP = 41, SLOT_COUNT_POS = 42, SLOT_COUNT_SCAN = 43, SLOT_COUNT_OUT = 44,
+    // all-pairs comparison: its figures; bottom-n: its scan (compare.hip)
+    SLOT_COMPARE_FIGURES = 45, SLOT_BOTTOM_SCAN = 46,
+    POOL_SLOTS = 48
+};
+
 struct bsk_ctx {
     BskOpts opt;
     int device = 0;
@@ -47,9 +81,9 @@ struct bsk_ctx {
     u64 *h_pinned = nullptr;  // [8] pinned host words for small read-backs
     u8 *d_lut = nullptr;      // codon tables of `lut_table` (kernels_translate.hpp layout)
     int lut_table = 0;
-    // tiled calls: grow-only temporaries (hipMalloc / hipFree of ten buffers per call cost more than the kernels)
-    void *tmp[48] = {};      // 0-9: tiled calls / sets, 12-14: bsk_result_fetch, 16-19: bsk_result_compact, 20: bsk_sets_fetch_narrow, 21-23: class plans, 24-27: two-pass syncmers, 28-29: the ASCII side launch's own reference words / status bytes, 32-37: set operations (setops.hip), 40-44: counted sets (counts.hip), 45-46: all-pairs comparison / bottom-n (compare.hip)
-    size_t tmp_cap[48] = {};
+    // grow-only temporaries of the entries (hipMalloc / hipFree of a tiled call's ten buffers cost more than its kernels)
+    void *tmp[POOL_SLOTS] = {};  // one buffer per PoolSlot, taken through ctx_pool
+    size_t tmp_cap[POOL_SLOTS] = {};
     u64 *h_refs = nullptr;   // pinned staging of bsk_result_fetch (refs down, offsets up), grow-only
     size_t h_refs_cap = 0;
     struct bsk_result *tile_res = nullptr;  // tile-level result of the previous tiled call, reused
@@ -74,7 +108,7 @@ struct bsk_ctx {
     bool adopted_recorded = false;
     struct ClassSet *cls = nullptr;       // the class plan a run_planned / launch in progress belongs to (biosketch.hip: run_classed)
     bool no_side_fast = false;            // run_planned: a staged side kernel's region overflowed, plan the general one
-    struct bsk_result *cls_owner = nullptr;  // the result whose class plan the pooled lists / views (tmp 21-23) currently describe
+    struct bsk_result *cls_owner = nullptr;  // the result whose class plan the pooled lists / views (SLOT_CLASS_*) currently describe
     u64 sel_need = 0;           // two-pass syncmers: the dense region a call that is being sized again needs (run_planned)
     bool no_syn_pk = false;     // set while a call falls back from k_syncmer_pk / k_minimizer_pk (the list of reads for the exact machine filled up)
     bool no_prot_fast = false;
@@ -205,6 +239,7 @@ static inline int fail_arg(bsk_ctx *ctx, const char *what) {
         if (e__ != hipSuccess) return fail_hip(ctx, e__, #call); \
     } while (0)
 
+int grid_for(bsk_ctx *ctx, u64 items, int block) __attribute__((visibility("hidden")));  // biosketch.hip: workgroups of `block` items, at most 16 per CU
 bool spare_flush_all() __attribute__((visibility("hidden")));  // biosketch.hip
 // Every device allocation of the library's host code (this header is in all of its translation units): when the device is out of memory, what the contexts keep in reserve (released
 // results' arrays) goes back first, then the allocation is tried once more.
@@ -217,3 +252,28 @@ static inline hipError_t bsk_malloc_retry(void **p, size_t bytes) {
     return e;
 }
 #define hipMalloc(ptr, bytes) bsk_malloc_retry((void **)(ptr), (bytes))
+
+// The library's one grow-only allocator (below the macro: it flushes and retries like every other allocation).  A buffer is kept while it
+// holds `bytes` and exists -- so a request of no bytes still yields a pointer -- and is otherwise freed BEFORE its successor is allocated
+// (the peak stays one buffer), with a quarter and 256 bytes of slack so that a slowly growing caller settles.  hipMalloc / hipFree
+// synchronise the whole device and cost more than the kernels of a small call: in steady state neither runs.
+// An object's own array: *cap is what *p holds, in bytes.  slack == false: exactly `bytes` (an object made for one call).  On failure the
+// array is gone (*p NULL, *cap 0).  Out of line: the library has some ninety call sites and none of them is hot.
+template <class T>
+static inline __attribute__((noinline)) hipError_t grow_array(T **p, size_t *cap, size_t bytes, bool slack = true) {
+    if (*cap >= bytes && *p) return hipSuccess;
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const size_t want = slack ? bytes + bytes / 4 + 256 : bytes;
+    const hipError_t e = hipMalloc(p, want);
+    if (e == hipSuccess) *cap = want;
+    return e;
+}
+// Slot `slot` of the context's pool, at least `bytes` big.
+template <class T>
+static inline hipError_t ctx_pool(bsk_ctx *ctx, PoolSlot slot, size_t bytes, T **out) {
+    const hipError_t e = grow_array(&ctx->tmp[slot], &ctx->tmp_cap[slot], bytes);
+    *out = static_cast<T *>(ctx->tmp[slot]);
+    return e;
+}

@@ -154,22 +154,16 @@ int launch(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, bsk_result *re
         return BSK_OK;
     };
     bool side_early = false;
+    u64 *side_refs = nullptr;  // side_early: the side launch's own reference words and status bytes (pooled), for k_adopt_side below
+    u8 *side_status = nullptr;
     if (pl.mixed && kind_has_pos(p->kind) && !ctx->opt.no_side_early && side_ctx(ctx)) {
         bsk_ctx *sc = ctx->side;
-        auto grow = [&](int slot, size_t bytes) -> hipError_t {
-            if (ctx->tmp_cap[slot] >= bytes) return hipSuccess;
-            (void)hipFree(ctx->tmp[slot]);
-            ctx->tmp[slot] = nullptr;
-            ctx->tmp_cap[slot] = 0;
-            const hipError_t e = hipMalloc(&ctx->tmp[slot], bytes + bytes / 4 + 256);
-            if (e == hipSuccess) ctx->tmp_cap[slot] = bytes + bytes / 4 + 256;
-            return e;
-        };
-        if (ensure_scratch(sc, pl.side_nunits, 0) == BSK_OK && grow(28, (size_t)b->n * 8) == hipSuccess && grow(29, (size_t)b->n) == hipSuccess) {
+        if (ensure_scratch(sc, pl.side_nunits, 0) == BSK_OK && ctx_pool(ctx, SLOT_SIDE_REFS, (size_t)b->n * 8, &side_refs) == hipSuccess &&
+            ctx_pool(ctx, SLOT_SIDE_STATUS, (size_t)b->n, &side_status) == hipSuccess) {
             // (behind the counters' memsets above: the side kernel's ticket and total live beside the main kernel's)
             HIPCHK(ctx, hipEventRecord(ctx->ev_mix0, ctx->stream));
             HIPCHK(ctx, hipStreamWaitEvent(sc->stream, ctx->ev_mix0, 0));
-            const int src = side_launch(sc->stream, sc->d_lookback, (u64 *)ctx->tmp[28], (u8 *)ctx->tmp[29]);
+            const int src = side_launch(sc->stream, sc->d_lookback, side_refs, side_status);
             if (src != BSK_OK) return src;
             side_early = true;
         } else {
@@ -218,23 +212,10 @@ int launch(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, bsk_result *re
             const u32 ns_max = b->maxlen + 1 > (u32)p->s ? b->maxlen - (u32)p->s + 1 : 1;
             const u32 nb = (ns_max + (u32)pl.fast_w - 1) / (u32)pl.fast_w;  // fused blocks: i0 = W, 2W, ... < ns_max (one spare)
             const u32 nblocks = (pl.nunits + 1023u) / 1024u;
-            auto pool = [&](int slot, size_t bytes, void **outp) -> hipError_t {
-                if (ctx->tmp_cap[slot] < bytes) {
-                    (void)hipFree(ctx->tmp[slot]);
-                    ctx->tmp[slot] = nullptr;
-                    ctx->tmp_cap[slot] = 0;
-                    const size_t want = bytes + bytes / 4 + 256;
-                    const hipError_t e = hipMalloc(&ctx->tmp[slot], want);
-                    if (e != hipSuccess) return e;
-                    ctx->tmp_cap[slot] = want;
-                }
-                *outp = ctx->tmp[slot];
-                return hipSuccess;
-            };
-            HIPCHK(ctx, pool(24, (size_t)pl.nunits * nb * 64 * 4, (void **)&a.sel_mask));
-            HIPCHK(ctx, pool(25, (size_t)pl.nunits * 64 * 4, (void **)&a.sel_cnt));
-            HIPCHK(ctx, pool(26, (size_t)pl.nunits * 4 + 64, (void **)&a.sel_utot));
-            HIPCHK(ctx, pool(27, ((size_t)pl.nunits + nblocks + 8) * 8, (void **)&a.sel_ubase));
+            HIPCHK(ctx, ctx_pool(ctx, SLOT_SEL_MASK, (size_t)pl.nunits * nb * 64 * 4, &a.sel_mask));
+            HIPCHK(ctx, ctx_pool(ctx, SLOT_SEL_CNT, (size_t)pl.nunits * 64 * 4, &a.sel_cnt));
+            HIPCHK(ctx, ctx_pool(ctx, SLOT_SEL_UTOT, (size_t)pl.nunits * 4 + 64, &a.sel_utot));
+            HIPCHK(ctx, ctx_pool(ctx, SLOT_SEL_UBASE, ((size_t)pl.nunits + nblocks + 8) * 8, &a.sel_ubase));
             a.sel_lookback = a.sel_ubase + pl.nunits;
             a.sel_nb = nb;
             HIPCHK(ctx, hipMemsetAsync(a.sel_lookback, 0, (size_t)nblocks * 8, ctx->stream));
@@ -298,7 +279,7 @@ int launch(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, bsk_result *re
     if (side_early) {  // ... or it ran beside the main kernel (below): its reference words and status bytes replace the main kernel's
         HIPCHK(ctx, hipEventRecord(ctx->ev_mix1, ctx->side->stream));
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_mix1, 0));
-        hipLaunchKernelGGL(k_adopt_side, dim3(grid_for(ctx, b->nsub, 256)), dim3(256), 0, ctx->stream, b->subset, (u64)b->nsub, (const u64 *)ctx->tmp[28], (const u8 *)ctx->tmp[29],
+        hipLaunchKernelGGL(k_adopt_side, dim3(grid_for(ctx, b->nsub, 256)), dim3(256), 0, ctx->stream, b->subset, (u64)b->nsub, (const u64 *)side_refs, (const u8 *)side_status,
                            res->refs, res->status);
     }
     if (ev1) HIPCHK(ctx, hipEventRecord(ev1, ctx->stream));

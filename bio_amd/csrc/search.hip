@@ -534,11 +534,6 @@ __global__ __launch_bounds__(256) void k_off_u32(const u64 *in, u64 n, u32 *out)
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) out[i] = (u32)in[i];
 }
 
-unsigned grid_for(const bsk_ctx *ctx, u64 items, u64 per_block, u64 blocks_per_cu) {
-    const u64 g = (items + per_block - 1) / per_block;
-    return (unsigned)std::max<u64>(1, std::min<u64>(g, (u64)ctx->cus * blocks_per_cu));
-}
-
 // device temporaries of one call, freed on every way out
 struct Temps {
     std::vector<void *> p;
@@ -552,34 +547,6 @@ struct Temps {
         return e;
     }
 };
-// a grow-only temporary of the context (slots 10, 11, 15, 30, 31: the search's), carved into aligned pieces
-hipError_t pool_get(bsk_ctx *ctx, int slot, size_t bytes, void **out) {
-    if (ctx->tmp_cap[slot] < bytes || !ctx->tmp[slot]) {
-        (void)hipFree(ctx->tmp[slot]);
-        ctx->tmp[slot] = nullptr;
-        ctx->tmp_cap[slot] = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(&ctx->tmp[slot], want);
-        if (e != hipSuccess) return e;
-        ctx->tmp_cap[slot] = want;
-    }
-    *out = ctx->tmp[slot];
-    return hipSuccess;
-}
-struct Carve {
-    size_t bytes = 0;
-    template <class T>
-    size_t add(u64 n) {  // offset of an array of n T, 256-byte aligned
-        const size_t at = bytes;
-        bytes += ((n ? n : 1) * sizeof(T) + 255) & ~(size_t)255;
-        return at;
-    }
-};
-template <class T>
-T *at(void *base, size_t off) {
-    return reinterpret_cast<T *>(static_cast<char *>(base) + off);
-}
-
 }  // namespace
 
 extern "C" int bsk_sets_from_host(bsk_ctx *ctx, const uint64_t *offsets, uint64_t n_sets, const uint64_t *values, bsk_sets **out) {
@@ -717,7 +684,7 @@ extern "C" int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index 
         HIPCHK(ctx, rocprim::radix_sort_pairs(stmp, tb, kin, kout, tin, ix->a->post_tgt, (size_t)P, 0, 64, st));
         flag = tin;  // (both free after the sort)
         pos = kin;
-        HIPCHK(ctx, tmp.get((void **)&part, ((P + SCAN_CHUNK - 1) / SCAN_CHUNK + 2) * 8));
+        HIPCHK(ctx, tmp.get((void **)&part, (scan_parts(P)) * 8));
         hipLaunchKernelGGL(k_run_heads, dim3(grid_for(ctx, P, 256, 16)), dim3(256), 0, st, kout, P, flag);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, scan_counts(st, KeepOf{flag}, P, part, pos, tot, (u64 *)nullptr));
@@ -801,28 +768,18 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
     hipStream_t st = ctx->stream;
     const u64 nq = qs->n_sets, nv = qs->n_values, T = ix->n_targets;
     const Thr thr{sp->min_shared ? sp->min_shared : 1u, sp->min_query_cov, sp->min_target_cov};
-    auto grow = [&](void **p, size_t *cap, size_t bytes) -> hipError_t {  // the hits' own arrays: grow-only
-        if (*cap >= bytes && *p) return hipSuccess;
-        (void)hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(p, want);
-        if (e == hipSuccess) *cap = want;
-        return e;
-    };
     res->n_queries = nq;
     res->n_hits = 0;
     res->n_large = 0;
-    HIPCHK(ctx, grow((void **)&res->offsets, &res->c_offsets, (nq + 1) * 8));
-    // per-query arrays (slot 10) and the query values' posting ranges (slot 11)
+    HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (nq + 1) * 8));
+    // per-query arrays (one carved buffer) and the query values' posting ranges
     Carve cq;
     const size_t o_qsum = cq.add<u64>(nq), o_stage = cq.add<u64>(nq + 1), o_hcnt = cq.add<u64>(nq), o_lslot = cq.add<u64>(nq + 1),
-                 o_loff = cq.add<u64>(nq + 1), o_part = cq.add<u64>((nq + SCAN_CHUNK - 1) / SCAN_CHUNK + 2), o_tot = cq.add<u64>(8),
+                 o_loff = cq.add<u64>(nq + 1), o_part = cq.add<u64>(scan_parts(nq)), o_tot = cq.add<u64>(8),
                  o_lq = cq.add<u32>(nq);
     void *bq = nullptr, *brng = nullptr;
-    HIPCHK(ctx, pool_get(ctx, 10, cq.bytes, &bq));
-    HIPCHK(ctx, pool_get(ctx, 11, (nv ? nv : 1) * 8, &brng));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SEARCH_QUERY, cq.bytes, &bq));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SEARCH_RANGES, (nv ? nv : 1) * 8, &brng));
     u64 *qsum = at<u64>(bq, o_qsum), *stage_off = at<u64>(bq, o_stage), *hcnt = at<u64>(bq, o_hcnt), *lslot = at<u64>(bq, o_lslot),
         *loff = at<u64>(bq, o_loff), *part = at<u64>(bq, o_part), *tot = at<u64>(bq, o_tot), *rng = static_cast<u64 *>(brng);
     u32 *lq = at<u32>(bq, o_lq);
@@ -841,7 +798,7 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
     HIPCHK(ctx, hipStreamSynchronize(st));
     const u64 S = ctx->h_pinned[0], L = ctx->h_pinned[1], NL = ctx->h_pinned[2];
     void *bst = nullptr;
-    HIPCHK(ctx, pool_get(ctx, 15, (S ? S : 1) * 8, &bst));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SEARCH_STAGE, (S ? S : 1) * 8, &bst));
     u32 *st_tgt = static_cast<u32 *>(bst), *st_sh = st_tgt + (S ? S : 1);
     // C. queries of at most SR_CAP target ids
     if (nq) {
@@ -853,9 +810,9 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
     if (NL) {
         Carve cl;
         const size_t o_in = cl.add<u64>(L + 1), o_out = cl.add<u64>(L), o_rstart = cl.add<u64>(L + 1), o_kpos = cl.add<u64>(L + 1),
-                     o_flag = cl.add<u32>(L), o_sfirst = cl.add<u64>(NL), o_part2 = cl.add<u64>((L + SCAN_CHUNK - 1) / SCAN_CHUNK + 2);
+                     o_flag = cl.add<u32>(L), o_sfirst = cl.add<u64>(NL), o_part2 = cl.add<u64>(scan_parts(L));
         void *bl = nullptr;
-        HIPCHK(ctx, pool_get(ctx, 30, cl.bytes, &bl));
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_SEARCH_LARGE, cl.bytes, &bl));
         u64 *lin = at<u64>(bl, o_in), *lout = at<u64>(bl, o_out), *rstart = at<u64>(bl, o_rstart), *kpos = at<u64>(bl, o_kpos), *sfirst = at<u64>(bl, o_sfirst),
             *part2 = at<u64>(bl, o_part2);
         u32 *flag = at<u32>(bl, o_flag);
@@ -866,7 +823,7 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
         size_t tb = 0;
         HIPCHK(ctx, sets_sort_u64(nullptr, tb, lin, lout, (size_t)L, 0, end_bit, st));
         void *stmp = nullptr;
-        HIPCHK(ctx, pool_get(ctx, 31, tb ? tb : 8, &stmp));
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_SEARCH_SORT_TMP, tb ? tb : 8, &stmp));
         HIPCHK(ctx, sets_sort_u64(stmp, tb, lin, lout, (size_t)L, 0, end_bit, st));
         u64 *ridx = lin;  // (free after the sort; L + 1 entries)
         hipLaunchKernelGGL(k_run_heads, dim3(grid_for(ctx, L, 256, 16)), dim3(256), 0, st, lout, L, flag);
@@ -886,8 +843,8 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot + 5, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     const u64 H = ctx->h_pinned[0];
-    HIPCHK(ctx, grow((void **)&res->target, &res->c_target, (H ? H : 1) * 4));
-    HIPCHK(ctx, grow((void **)&res->shared, &res->c_shared, (H ? H : 1) * 4));
+    HIPCHK(ctx, grow_array(&res->target, &res->c_target, (H ? H : 1) * 4));
+    HIPCHK(ctx, grow_array(&res->shared, &res->c_shared, (H ? H : 1) * 4));
     if (H) {
         hipLaunchKernelGGL(k_sr_move, dim3(grid_for(ctx, nq * 16, 256, 32)), dim3(256), 0, st, stage_off, res->offsets, hcnt, nq, st_tgt, st_sh, res->target,
                            res->shared);
@@ -928,26 +885,16 @@ static int top_impl(bsk_ctx *ctx, const bsk_hits *h, u32 n, bsk_hits *res) {
     hipStream_t st = ctx->stream;
     const u64 nq = h->n_queries, Hin = h->n_hits;
     const bool select = n <= TOP_SELECT_N;  // else: LDS sort, and the sort path beyond TOP_LDS_KEYS hits
-    auto grow = [&](void **p, size_t *cap, size_t bytes) -> hipError_t {
-        if (*cap >= bytes && *p) return hipSuccess;
-        (void)hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(p, want);
-        if (e == hipSuccess) *cap = want;
-        return e;
-    };
     res->n_queries = nq;
     res->n_hits = 0;
     res->n_large = 0;
-    HIPCHK(ctx, grow((void **)&res->offsets, &res->c_offsets, (nq + 1) * 8));
+    HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (nq + 1) * 8));
     // scratch: the search's own slots (its temporaries are dead once its hits exist)
     Carve cq;
-    const size_t o_part = cq.add<u64>((nq + SCAN_CHUNK - 1) / SCAN_CHUNK + 2), o_tot = cq.add<u64>(8), o_lslot = cq.add<u64>(select ? 1 : nq + 1),
+    const size_t o_part = cq.add<u64>(scan_parts(nq)), o_tot = cq.add<u64>(8), o_lslot = cq.add<u64>(select ? 1 : nq + 1),
                  o_loff = cq.add<u64>(select ? 1 : nq + 1), o_lq = cq.add<u32>(select ? 1 : nq);
     void *bq = nullptr;
-    HIPCHK(ctx, pool_get(ctx, 10, cq.bytes, &bq));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SEARCH_QUERY, cq.bytes, &bq));
     u64 *part = at<u64>(bq, o_part), *tot = at<u64>(bq, o_tot), *lslot = at<u64>(bq, o_lslot), *loff = at<u64>(bq, o_loff);
     u32 *lq = at<u32>(bq, o_lq);
     // [0] hits kept, [1] hits of the sort path's queries, [2] those queries, [3] the most hits one of them has, [4] the largest shared count,
@@ -970,8 +917,8 @@ static int top_impl(bsk_ctx *ctx, const bsk_hits *h, u32 n, bsk_hits *res) {
     HIPCHK(ctx, hipStreamSynchronize(st));
     const u64 H = ctx->h_pinned[0], L = ctx->h_pinned[1], NL = ctx->h_pinned[2], maxc = ctx->h_pinned[3], maxs = ctx->h_pinned[4], n_group = ctx->h_pinned[5],
               n_wave = ctx->h_pinned[6];
-    HIPCHK(ctx, grow((void **)&res->target, &res->c_target, (H ? H : 1) * 4));
-    HIPCHK(ctx, grow((void **)&res->shared, &res->c_shared, (H ? H : 1) * 4));
+    HIPCHK(ctx, grow_array(&res->target, &res->c_target, (H ? H : 1) * 4));
+    HIPCHK(ctx, grow_array(&res->shared, &res->c_shared, (H ? H : 1) * 4));
     if (n_group) {
         hipLaunchKernelGGL(k_top_group, dim3(grid_for(ctx, nq * 16, 256, 32)), dim3(256), 0, st, h->offsets, h->target, h->shared, nq, n, res->offsets, res->target,
                            res->shared);
@@ -998,14 +945,14 @@ static int top_impl(bsk_ctx *ctx, const bsk_hits *h, u32 n, bsk_hits *res) {
         Carve cl;
         const size_t o_in = cl.add<u64>(L), o_out = cl.add<u64>(L);
         void *bl = nullptr, *stmp = nullptr;
-        HIPCHK(ctx, pool_get(ctx, 30, cl.bytes, &bl));
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_SEARCH_LARGE, cl.bytes, &bl));
         u64 *lin = at<u64>(bl, o_in), *lout = at<u64>(bl, o_out);
         hipLaunchKernelGGL(k_top_list, dim3(grid_for(ctx, nq, 256, 8)), dim3(256), 0, st, h->offsets, nq, lslot, lq);
         hipLaunchKernelGGL(k_top_emit, dim3(grid_for(ctx, NL, 4, 16)), dim3(256), 0, st, h->offsets, h->shared, lq, NL, loff, maxs, bs, bp, lin);
         HIPCHK(ctx, hipGetLastError());
         size_t tb = 0;
         HIPCHK(ctx, sets_sort_u64(nullptr, tb, lin, lout, (size_t)L, 0, bs + bp + bslot, st));
-        HIPCHK(ctx, pool_get(ctx, 31, tb ? tb : 8, &stmp));
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_SEARCH_SORT_TMP, tb ? tb : 8, &stmp));
         HIPCHK(ctx, sets_sort_u64(stmp, tb, lin, lout, (size_t)L, 0, bs + bp + bslot, st));
         hipLaunchKernelGGL(k_top_place, dim3(grid_for(ctx, L, 256, 16)), dim3(256), 0, st, lout, L, h->offsets, h->target, lq, loff, maxs, bs, bp, n, res->offsets,
                            res->target, res->shared);
@@ -1028,7 +975,7 @@ int hits_fetch_narrow(bsk_ctx *ctx, const bsk_hits *h, uint32_t *offsets, uint32
     HIPCHK(ctx, hipSetDevice(ctx->device));
     void *o32 = nullptr;
     const size_t need = (h->n_queries + 1) * 4;
-    HIPCHK(ctx, pool_get(ctx, 20, need, &o32));  // (bsk_sets_fetch_narrow's slot: both use it between two synchronisations of the stream)
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_NARROW_OFFS, need, &o32));
     hipLaunchKernelGGL(k_off_u32, dim3(grid_for(ctx, h->n_queries + 1, 256, 8)), dim3(256), 0, ctx->stream, h->offsets, h->n_queries + 1, (u32 *)o32);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(offsets, o32, need, hipMemcpyDeviceToHost, ctx->stream));

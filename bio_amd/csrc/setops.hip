@@ -366,49 +366,6 @@ __global__ void k_rd_offsets(const u64 *goff, const u64 *pos, u64 G, u64 n_in, u
         offs_out[g] = goff[g] < n_in ? pos[goff[g]] : n_out;
 }
 
-unsigned so_grid(const bsk_ctx *ctx, u64 items, u64 per_block, u64 blocks_per_cu) {
-    const u64 g = (items + per_block - 1) / per_block;
-    return (unsigned)std::max<u64>(1, std::min<u64>(g, (u64)ctx->cus * blocks_per_cu));
-}
-// grow-only temporaries of the context (slots 32-37: the set operations'), carved into aligned pieces
-hipError_t so_pool(bsk_ctx *ctx, int slot, size_t bytes, void **out) {
-    if (ctx->tmp_cap[slot] < bytes || !ctx->tmp[slot]) {
-        (void)hipFree(ctx->tmp[slot]);
-        ctx->tmp[slot] = nullptr;
-        ctx->tmp_cap[slot] = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(&ctx->tmp[slot], want);
-        if (e != hipSuccess) return e;
-        ctx->tmp_cap[slot] = want;
-    }
-    *out = ctx->tmp[slot];
-    return hipSuccess;
-}
-struct Carve {
-    size_t bytes = 0;
-    template <class T>
-    size_t add(u64 n) {  // offset of an array of n T, 256-byte aligned
-        const size_t at = bytes;
-        bytes += ((n ? n : 1) * sizeof(T) + 255) & ~(size_t)255;
-        return at;
-    }
-};
-template <class T>
-T *at(void *base, size_t off) {
-    return reinterpret_cast<T *>(static_cast<char *>(base) + off);
-}
-hipError_t so_grow(u64 **p, size_t *cap, size_t bytes) {  // the result's own arrays: grow-only
-    if (*cap >= bytes && *p) return hipSuccess;
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = bytes + bytes / 4 + 256;
-    const hipError_t e = hipMalloc(p, want);
-    if (e == hipSuccess) *cap = want;
-    return e;
-}
-u64 scan_parts(u64 n) { return (n + SCAN_CHUNK - 1) / SCAN_CHUNK + 2; }
-
 // SP = SoSpan, COUNTED = false: bsk_sets_op; SoSpanAB, true: bsk_sets_op_counted (the count pass is the same, the write pass also
 // writes res->counts)
 template <class SP, bool COUNTED>
@@ -420,9 +377,9 @@ int op_impl(bsk_ctx *ctx, const SP sp, const u64 n, bool broadcast, const bsk_se
     res->counted = false;
     res->plan[0] = 0;
     res->by_path[0] = res->by_path[1] = res->by_path[2] = 0;
-    HIPCHK(ctx, so_grow(&res->offsets, &res->c_offsets, (n + 1) * 8));
+    HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (n + 1) * 8));
     if (n == 0) {
-        HIPCHK(ctx, so_grow(&res->values, &res->c_values, 8));
+        HIPCHK(ctx, grow_array(&res->values, &res->c_values, 8));
         if (COUNTED) HIPCHK(ctx, sets_grow_counts(res, 1, true));
         HIPCHK(ctx, hipMemsetAsync(res->offsets, 0, 8, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
@@ -434,7 +391,7 @@ int op_impl(bsk_ctx *ctx, const SP sp, const u64 n, bool broadcast, const bsk_se
     const size_t o_wslot = cp.add<u64>(n + 1), o_tfirst = cp.add<u64>(n + 1), o_tslot = cp.add<u64>(n + 1), o_cnt = cp.add<u64>(n), o_part = cp.add<u64>(scan_parts(n)),
                  o_tot = cp.add<u64>(8), o_list = cp.add<u32>(n);
     void *bp = nullptr;
-    HIPCHK(ctx, so_pool(ctx, 32, cp.bytes, &bp));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_OP_PAIRS, cp.bytes, &bp));
     u64 *wslot = at<u64>(bp, o_wslot), *tfirst = at<u64>(bp, o_tfirst), *tslot = at<u64>(bp, o_tslot), *cnt = at<u64>(bp, o_cnt), *part = at<u64>(bp, o_part),
         *tot = at<u64>(bp, o_tot);
     u32 *list = at<u32>(bp, o_list);
@@ -452,17 +409,17 @@ int op_impl(bsk_ctx *ctx, const SP sp, const u64 n, bool broadcast, const bsk_se
         Carve ct;
         const size_t o_tcnt = ct.add<u64>(NT), o_tpos = ct.add<u64>(NT + 1), o_part2 = ct.add<u64>(scan_parts(NT)), o_tpair = ct.add<u32>(NT), o_ta0 = ct.add<u32>(NT);
         void *bt = nullptr;
-        HIPCHK(ctx, so_pool(ctx, 33, ct.bytes, &bt));
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_OP_TILES, ct.bytes, &bt));
         tcnt = at<u64>(bt, o_tcnt);
         tpos = at<u64>(bt, o_tpos);
         part2 = at<u64>(bt, o_part2);
         tpair = at<u32>(bt, o_tpair);
         ta0 = at<u32>(bt, o_ta0);
-        hipLaunchKernelGGL(k_so_cuts<SP>, dim3(so_grid(ctx, NT, 256, 16)), dim3(256), 0, st, sp, a->values, b->values, tfirst, n, NT, tpair, ta0);
+        hipLaunchKernelGGL(k_so_cuts<SP>, dim3(grid_for(ctx, NT, 256, 16)), dim3(256), 0, st, sp, a->values, b->values, tfirst, n, NT, tpair, ta0);
     }
-    if (NW) hipLaunchKernelGGL(k_so_list<SP>, dim3(so_grid(ctx, n, 256, 16)), dim3(256), 0, st, SoWaveOf<SP>{sp}, wslot, n, list);
-    const unsigned g_group = so_grid(ctx, n, 16, SO_GROUP_BLOCKS_PER_CU), g_wave = so_grid(ctx, NW, SO_WAVES, SO_WAVE_BLOCKS_PER_CU),
-                   g_tile = so_grid(ctx, NT, SO_WAVES, SO_TILE_BLOCKS_PER_CU);
+    if (NW) hipLaunchKernelGGL(k_so_list<SP>, dim3(grid_for(ctx, n, 256, 16)), dim3(256), 0, st, SoWaveOf<SP>{sp}, wslot, n, list);
+    const unsigned g_group = grid_for(ctx, n, 16, SO_GROUP_BLOCKS_PER_CU), g_wave = grid_for(ctx, NW, SO_WAVES, SO_WAVE_BLOCKS_PER_CU),
+                   g_tile = grid_for(ctx, NT, SO_WAVES, SO_TILE_BLOCKS_PER_CU);
     // 2. count pass
     if (NG) hipLaunchKernelGGL((k_so_group<false, SP>), dim3(g_group), dim3(256), 0, st, sp, a->values, b->values, n, op, cnt, (const u64 *)nullptr, (u64 *)nullptr);
     if (NW)
@@ -477,7 +434,7 @@ int op_impl(bsk_ctx *ctx, const SP sp, const u64 n, bool broadcast, const bsk_se
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot + 4, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     const u64 M = ctx->h_pinned[0];
-    HIPCHK(ctx, so_grow(&res->values, &res->c_values, (M ? M : 1) * 8));
+    HIPCHK(ctx, grow_array(&res->values, &res->c_values, (M ? M : 1) * 8));
     if (COUNTED) HIPCHK(ctx, sets_grow_counts(res, M ? M : 1, true));
     // 4. write pass: the same kernels, every kept value to its final place (c: nothing, or the counts that ride along)
     auto write = [&](auto... c) {
@@ -518,9 +475,9 @@ int reduce_impl(bsk_ctx *ctx, const bsk_sets *s, const uint64_t *group_offsets, 
     res->counted = false;
     res->plan[0] = 0;
     res->by_path[0] = res->by_path[1] = res->by_path[2] = 0;
-    HIPCHK(ctx, so_grow(&res->offsets, &res->c_offsets, (G + 1) * 8));
+    HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (G + 1) * 8));
     if (G == 0 || N == 0) {
-        HIPCHK(ctx, so_grow(&res->values, &res->c_values, 8));
+        HIPCHK(ctx, grow_array(&res->values, &res->c_values, 8));
         HIPCHK(ctx, hipMemsetAsync(res->offsets, 0, (G + 1) * 8, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
         snprintf(res->plan, sizeof res->plan, "bsk_sets_reduce: no values");
@@ -531,30 +488,30 @@ int reduce_impl(bsk_ctx *ctx, const bsk_sets *s, const uint64_t *group_offsets, 
     Carve cv;
     const size_t o_pos = cv.add<u64>(N + 1), o_part = cv.add<u64>(scan_parts(N)), o_keep = cv.add<u32>(N);
     void *bg = nullptr, *bsorted = nullptr, *bv = nullptr, *btmp = nullptr;
-    HIPCHK(ctx, so_pool(ctx, 34, cg.bytes, &bg));
-    HIPCHK(ctx, so_pool(ctx, 35, N * 8, &bsorted));
-    HIPCHK(ctx, so_pool(ctx, 36, cv.bytes, &bv));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_REDUCE_GROUPS, cg.bytes, &bg));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_REDUCE_SORTED, N * 8, &bsorted));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_REDUCE_VALUES, cv.bytes, &bv));
     u64 *gmem = at<u64>(bg, o_gmem), *goff = at<u64>(bg, o_goff), *tot = at<u64>(bg, o_tot), *sorted = static_cast<u64 *>(bsorted), *pos = at<u64>(bv, o_pos),
         *part = at<u64>(bv, o_part);
     u32 *keep = at<u32>(bv, o_keep);
     HIPCHK(ctx, hipMemsetAsync(tot, 0, 64, st));
     HIPCHK(ctx, hipMemcpyAsync(gmem, group_offsets, (G + 1) * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_rd_goff, dim3(so_grid(ctx, G + 1, 256, 16)), dim3(256), 0, st, s->offsets, gmem, G + 1, goff);
+    hipLaunchKernelGGL(k_rd_goff, dim3(grid_for(ctx, G + 1, 256, 16)), dim3(256), 0, st, s->offsets, gmem, G + 1, goff);
     HIPCHK(ctx, hipGetLastError());
     // every group's range of the values array, sorted (sets.hip's instantiation of the segmented radix sort)
     size_t tb = 0;
     HIPCHK(ctx, sets_sort_segments_u64(nullptr, tb, s->values, sorted, N, G, goff, st));
-    HIPCHK(ctx, so_pool(ctx, 37, tb ? tb : 8, &btmp));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_REDUCE_SORT_TMP, tb ? tb : 8, &btmp));
     HIPCHK(ctx, sets_sort_segments_u64(btmp, tb, s->values, sorted, N, G, goff, st));
-    hipLaunchKernelGGL(k_rd_flags, dim3(so_grid(ctx, N, RD_CHUNK, 16)), dim3(256), 0, st, sorted, N, goff, gmem, G, min_members, keep);
+    hipLaunchKernelGGL(k_rd_flags, dim3(grid_for(ctx, N, RD_CHUNK, 16)), dim3(256), 0, st, sorted, N, goff, gmem, G, min_members, keep);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, scan_counts(st, KeepOf{keep}, N, part, pos, tot, (u64 *)nullptr));
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));  // (the caller's group_offsets are not needed past this point)
     const u64 M = ctx->h_pinned[0];
-    HIPCHK(ctx, so_grow(&res->values, &res->c_values, (M ? M : 1) * 8));
-    if (M) hipLaunchKernelGGL(k_rd_scatter, dim3(so_grid(ctx, N, 256, 16)), dim3(256), 0, st, sorted, keep, pos, N, res->values);
-    hipLaunchKernelGGL(k_rd_offsets, dim3(so_grid(ctx, G + 1, 256, 16)), dim3(256), 0, st, goff, pos, G, N, M, res->offsets);
+    HIPCHK(ctx, grow_array(&res->values, &res->c_values, (M ? M : 1) * 8));
+    if (M) hipLaunchKernelGGL(k_rd_scatter, dim3(grid_for(ctx, N, 256, 16)), dim3(256), 0, st, sorted, keep, pos, N, res->values);
+    hipLaunchKernelGGL(k_rd_offsets, dim3(grid_for(ctx, G + 1, 256, 16)), dim3(256), 0, st, goff, pos, G, N, M, res->offsets);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(st));
     res->n_values = M;

@@ -285,11 +285,6 @@ __global__ __launch_bounds__(256) void k_move_groups(const u64 *tmp, const u64 *
         }
     }
 }
-int grid_of(bsk_ctx *ctx, u64 items, int block) {
-    const u64 g = (items + block - 1) / block;
-    return (int)std::max<u64>(1, std::min<u64>(g, (u64)ctx->cus * 16));
-}
-
 }  // namespace
 
 // Dense device copy of a result's tuples: the sketch kernels leave gaps between the 64-sequence units' slabs, a device-side consumer
@@ -440,19 +435,6 @@ extern "C" int bsk_result_compact(bsk_ctx *ctx, const bsk_result *r, const uint6
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const u64 n = r->n;
-    auto pool = [&](int slot, size_t bytes, void **outp) -> hipError_t {
-        if (ctx->tmp_cap[slot] < bytes) {
-            (void)hipFree(ctx->tmp[slot]);
-            ctx->tmp[slot] = nullptr;
-            ctx->tmp_cap[slot] = 0;
-            const size_t want = bytes + bytes / 4 + 256;
-            const hipError_t e = hipMalloc(&ctx->tmp[slot], want);
-            if (e != hipSuccess) return e;
-            ctx->tmp_cap[slot] = want;
-        }
-        *outp = ctx->tmp[slot];
-        return hipSuccess;
-    };
     u64 *offs = nullptr, *part = nullptr, *oh = nullptr;
     u32 *op = nullptr;
     const bool timing = ctx->opt.timing;  // dev: wall time of the phases, to stderr
@@ -460,26 +442,26 @@ extern "C" int bsk_result_compact(bsk_ctx *ctx, const bsk_result *r, const uint6
     auto lap = [&](const char *what) {
         if (timing) fprintf(stderr, "bsk_result_compact: %-18s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     };
-    HIPCHK(ctx, pool(16, (n + 2) * 8, (void **)&offs));
-    HIPCHK(ctx, pool(17, ((n + SCAN_CHUNK - 1) / SCAN_CHUNK + 2) * 8, (void **)&part));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_COMPACT_OFFS, (n + 2) * 8, &offs));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SCAN_PART, scan_parts(n) * 8, &part));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_total, 0, 16, st));
     HIPCHK(ctx, scan_counts(st, CountOf{r->refs, r->wfirst, r->wcount}, n, part, offs, ctx->d_total + 1, (u64 *)nullptr));
     u64 T = 0;
     HIPCHK(ctx, hipMemcpyAsync(&T, ctx->d_total + 1, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     lap("offsets scanned");
-    HIPCHK(ctx, pool(18, (T + 1) * 8, (void **)&oh));
-    if (r->pos) HIPCHK(ctx, pool(19, (T + 1) * 4, (void **)&op));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_COMPACT_HASH, (T + 1) * 8, &oh));
+    if (r->pos) HIPCHK(ctx, ctx_pool(ctx, SLOT_COMPACT_POS, (T + 1) * 4, &op));
     lap("arrays");
     if (T) {
         if (r->refs && !ctx->opt.no_group_gather && r->unit_rows)  // unit rows
-            hipLaunchKernelGGL((k_gather_groups<false, true>), dim3(grid_of(ctx, n + 64, 1)), dim3(64), 0, st, r->hash, r->pos, r->refs, offs, n, oh, (void *)op,
+            hipLaunchKernelGGL((k_gather_groups<false, true>), dim3(grid_for(ctx, n + 64, 1)), dim3(64), 0, st, r->hash, r->pos, r->refs, offs, n, oh, (void *)op,
                                (u32 *)nullptr, (u32 *)nullptr);
         else if (r->refs && !ctx->opt.no_group_gather)
-            hipLaunchKernelGGL((k_gather_groups<false, false>), dim3(grid_of(ctx, n + 64, 256)), dim3(256), 0, st, r->hash, r->pos, r->refs, offs, n, oh, (void *)op,
+            hipLaunchKernelGGL((k_gather_groups<false, false>), dim3(grid_for(ctx, n + 64, 256)), dim3(256), 0, st, r->hash, r->pos, r->refs, offs, n, oh, (void *)op,
                                (u32 *)nullptr, (u32 *)nullptr);
         else
-            hipLaunchKernelGGL(k_compact, dim3(grid_of(ctx, n * 64, 256)), dim3(256), 0, st, r->hash, r->pos, r->refs, r->wfirst, r->wcount, offs, n, oh,
+            hipLaunchKernelGGL(k_compact, dim3(grid_for(ctx, n * 64, 256)), dim3(256), 0, st, r->hash, r->pos, r->refs, r->wfirst, r->wcount, offs, n, oh,
                                r->pos ? op : nullptr);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipStreamSynchronize(st));
@@ -528,25 +510,12 @@ extern "C" int bsk_result_fetch_narrow(bsk_ctx *ctx, const bsk_result *r, uint64
     if (pos && !r->pos) return fail_arg(ctx, "bsk_result_fetch_narrow: this kind has implicit positions");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    auto pool = [&](int slot, size_t bytes, void **outp) -> hipError_t {
-        if (ctx->tmp_cap[slot] < bytes) {
-            (void)hipFree(ctx->tmp[slot]);
-            ctx->tmp[slot] = nullptr;
-            ctx->tmp_cap[slot] = 0;
-            const size_t want = bytes + bytes / 4 + 256;
-            const hipError_t e = hipMalloc(&ctx->tmp[slot], want);
-            if (e != hipSuccess) return e;
-            ctx->tmp_cap[slot] = want;
-        }
-        *outp = ctx->tmp[slot];
-        return hipSuccess;
-    };
     u64 *offs = nullptr, *part = nullptr, *oh = nullptr;
     u16 *op = nullptr;
     u32 *oo = nullptr;
-    HIPCHK(ctx, pool(12, (count + 2) * 8 + (count + 2) * 4, (void **)&offs));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_FETCH_OFFS, (count + 2) * 8 + (count + 2) * 4, &offs));
     oo = reinterpret_cast<u32 *>(offs + count + 2);
-    HIPCHK(ctx, pool(17, ((count + SCAN_CHUNK - 1) / SCAN_CHUNK + 2) * 8, (void **)&part));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SCAN_PART, scan_parts(count) * 8, &part));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_total, 0, 32, st));
     HIPCHK(ctx, scan_counts(st, CountOf{r->refs ? r->refs + first : nullptr, r->refs ? nullptr : r->wfirst + first, r->refs ? nullptr : r->wcount + first}, count, part, offs,
                             ctx->d_total + 1, (u64 *)nullptr));
@@ -559,16 +528,16 @@ extern "C" int bsk_result_fetch_narrow(bsk_ctx *ctx, const bsk_result *r, uint64
     if (n_tuples) *n_tuples = T;
     if (T > tuple_cap) return fail_arg(ctx, "bsk_result_fetch_narrow: tuple_cap too small");
     if (T >= (1ULL << 32)) return fail_arg(ctx, "bsk_result_fetch_narrow: 2^32 tuples or more (fetch a smaller range)");
-    HIPCHK(ctx, pool(13, (T + 1) * 8, (void **)&oh));
-    if (pos) HIPCHK(ctx, pool(14, (T + 1) * 2, (void **)&op));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_FETCH_HASH, (T + 1) * 8, &oh));
+    if (pos) HIPCHK(ctx, ctx_pool(ctx, SLOT_FETCH_POS, (T + 1) * 2, &op));
     if (r->refs && !ctx->opt.no_group_gather && r->unit_rows)  // unit rows
-        hipLaunchKernelGGL((k_gather_groups<true, true>), dim3(grid_of(ctx, count + 64, 1)), dim3(64), 0, st, r->hash, pos ? r->pos : nullptr, r->refs + first, offs,
+        hipLaunchKernelGGL((k_gather_groups<true, true>), dim3(grid_for(ctx, count + 64, 1)), dim3(64), 0, st, r->hash, pos ? r->pos : nullptr, r->refs + first, offs,
                            count, oh, (void *)op, oo, reinterpret_cast<u32 *>(ctx->d_total + 3));
     else if (r->refs && !ctx->opt.no_group_gather)
-        hipLaunchKernelGGL((k_gather_groups<true, false>), dim3(grid_of(ctx, count + 64, 256)), dim3(256), 0, st, r->hash, pos ? r->pos : nullptr, r->refs + first, offs,
+        hipLaunchKernelGGL((k_gather_groups<true, false>), dim3(grid_for(ctx, count + 64, 256)), dim3(256), 0, st, r->hash, pos ? r->pos : nullptr, r->refs + first, offs,
                            count, oh, (void *)op, oo, reinterpret_cast<u32 *>(ctx->d_total + 3));
     else
-        hipLaunchKernelGGL(k_gather_narrow, dim3(grid_of(ctx, (count + 1) * 16, 256)), dim3(256), 0, st, r->hash, pos ? r->pos : nullptr,
+        hipLaunchKernelGGL(k_gather_narrow, dim3(grid_for(ctx, (count + 1) * 16, 256)), dim3(256), 0, st, r->hash, pos ? r->pos : nullptr,
                            r->refs ? r->refs + first : nullptr, r->refs ? nullptr : r->wfirst + first, r->refs ? nullptr : r->wcount + first, offs, count, oh, op, oo,
                            reinterpret_cast<u32 *>(ctx->d_total + 3));
     HIPCHK(ctx, hipGetLastError());
@@ -644,39 +613,16 @@ int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool cou
         if (code != BSK_OK && res) bsk_sets_release(res);
         return code;
     };
-    auto grow = [&](u64 **p, size_t *cap, size_t bytes) -> hipError_t {  // the sets' own arrays: grow-only
-        if (*cap >= bytes && *p) return hipSuccess;
-        (void)hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-        const size_t want = reuse ? bytes + bytes / 4 + 256 : bytes;
-        const hipError_t e = hipMalloc(p, want);
-        if (e == hipSuccess) *cap = want;
-        return e;
-    };
 #define SCHK(call)                                                  \
     do {                                                            \
         hipError_t e__ = (call);                                    \
         if (e__ != hipSuccess) return done(fail_hip(ctx, e__, #call)); \
     } while (0)
     // temporaries of every call come from the context's grow-only pool (hipMalloc / hipFree synchronise the device)
-    auto pool = [&](int slot, size_t bytes, void **outp) -> hipError_t {
-        if (ctx->tmp_cap[slot] < bytes) {
-            (void)hipFree(ctx->tmp[slot]);
-            ctx->tmp[slot] = nullptr;
-            ctx->tmp_cap[slot] = 0;
-            const size_t want = bytes + bytes / 4 + 256;
-            const hipError_t e = hipMalloc(&ctx->tmp[slot], want);
-            if (e != hipSuccess) return e;
-            ctx->tmp_cap[slot] = want;
-        }
-        *outp = ctx->tmp[slot];
-        return hipSuccess;
-    };
     // 1. where every sequence's values go in a dense copy: exclusive scan of the counts (+ the largest count)
     u64 *part = nullptr;
-    SCHK(pool(0, (n + 2) * 8, (void **)&offs));
-    SCHK(pool(1, ((n + SCAN_CHUNK - 1) / SCAN_CHUNK + 2) * 8, (void **)&part));
+    SCHK(ctx_pool(ctx, SLOT_SETS_OFFS, (n + 2) * 8, &offs));
+    SCHK(ctx_pool(ctx, SLOT_SETS_PART, scan_parts(n) * 8, &part));
     SCHK(hipMemsetAsync(ctx->d_total, 0, 16, st));  // [0] largest count, [1] total
     SCHK(scan_counts(st, CountOf{r->refs, r->wfirst, r->wcount}, n, part, offs, ctx->d_total + 1, ctx->d_total));
     u64 N = 0, max_count = 0;
@@ -696,8 +642,8 @@ int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool cou
     res->plan[0] = 0;  // (a re-used object may have been a set operation's result: bsk_sets_plan describes those only)
     res->by_path[0] = res->by_path[1] = res->by_path[2] = 0;
     res->counted = false;  // (a re-used counted object keeps its counts array, not its counts)
-    SCHK(grow(&res->offsets, &res->c_offsets, (n_sets + 1) * 8));
-    SCHK(grow(&res->values, &res->c_values, (N ? N : 1) * 8));
+    SCHK(grow_array(&res->offsets, &res->c_offsets, (n_sets + 1) * 8, reuse != nullptr));  // the sets' own arrays: grow-only; a fresh object gets exactly what it needs
+    SCHK(grow_array(&res->values, &res->c_values, (N ? N : 1) * 8, reuse != nullptr));
     if (N == 0) {
         SCHK(hipMemsetAsync(res->offsets, 0, (n_sets + 1) * 8, st));
         if (counted) SCHK(sets_grow_counts(res, 1, reuse != nullptr));
@@ -709,17 +655,17 @@ int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool cou
     if (scope == BSK_SETS_PER_SEQUENCE && max_count <= SMALL_CAP && !ctx->opt.sets_no_small && !counted) {
         // short reads: one sequence per row of 16 lanes, bitonic network over DPP moves (k_sets_rows)
         u64 *ucount = nullptr, *dense = nullptr;
-        SCHK(pool(2, N * 8, (void **)&dense));          // the sequences' distinct values at their input offsets
-        SCHK(pool(3, (n + 2) * 8, (void **)&ucount));
-        const unsigned sgrid = (unsigned)std::max<u64>(1, std::min<u64>((n + 15) / 16, (u64)ctx->cus * 32));
+        SCHK(ctx_pool(ctx, SLOT_SETS_VALUES, N * 8, &dense));          // the sequences' distinct values at their input offsets
+        SCHK(ctx_pool(ctx, SLOT_SETS_UCOUNT, (n + 2) * 8, &ucount));
+        const unsigned sgrid = grid_for(ctx, n, 16, 32);
         hipLaunchKernelGGL(k_sets_rows, dim3(sgrid), dim3(256), 0, st, r->hash, r->refs, r->wfirst, r->wcount, offs, n, maxhash, dense, ucount);
         SCHK(hipGetLastError());
         SCHK(scan_counts(st, ArrayOf{ucount}, n, part, res->offsets, ctx->d_total + 1, (u64 *)nullptr));
         if (!ctx->opt.no_group_gather)
-            hipLaunchKernelGGL(k_move_groups, dim3((unsigned)std::max<u64>(1, std::min<u64>((n + 255) / 256, (u64)ctx->cus * 16))), dim3(256), 0, st, dense, offs,
+            hipLaunchKernelGGL(k_move_groups, dim3(grid_for(ctx, n, 256, 16)), dim3(256), 0, st, dense, offs,
                                res->offsets, ucount, n, res->values);
         else
-            hipLaunchKernelGGL(k_move_seqs, dim3((unsigned)std::max<u64>(1, std::min<u64>((n + 7) / 8, (u64)ctx->cus * 32))), dim3(256), 0, st, dense, offs, res->offsets,
+            hipLaunchKernelGGL(k_move_seqs, dim3(grid_for(ctx, n, 8, 32)), dim3(256), 0, st, dense, offs, res->offsets,
                                ucount, n, res->values);
         SCHK(hipGetLastError());
         u64 M = 0;
@@ -729,9 +675,9 @@ int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool cou
         *out = res;
         return done(BSK_OK);
     }
-    SCHK(pool(2, N * 8, (void **)&vin));  // (all temporaries are pooled: in a process that has already cycled ~100 GB of batches a
-    SCHK(pool(5, N * 8, (void **)&vsorted));  //  hipMalloc / hipFree of these buffers cost 70-200 ms per call against 10-18 ms of kernels)
-    hipLaunchKernelGGL(k_gather_values, dim3(grid_of(ctx, n * 16, 256)), dim3(256), 0, st, r->hash, r->refs, r->wfirst, r->wcount, offs, n,
+    SCHK(ctx_pool(ctx, SLOT_SETS_VALUES, N * 8, &vin));  // (all temporaries are pooled: in a process that has already cycled ~100 GB of batches a
+    SCHK(ctx_pool(ctx, SLOT_SETS_SORTED, N * 8, &vsorted));  //  hipMalloc / hipFree of these buffers cost 70-200 ms per call against 10-18 ms of kernels)
+    hipLaunchKernelGGL(k_gather_values, dim3(grid_for(ctx, n * 16, 256)), dim3(256), 0, st, r->hash, r->refs, r->wfirst, r->wcount, offs, n,
                        maxhash, vin);
     SCHK(hipGetLastError());
     // 2. sort inside every set
@@ -741,35 +687,35 @@ int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool cou
         SCHK(hipStreamSynchronize(st));                           // the gather above still reads offs
         SCHK(hipMemcpy(offs, two, 16, hipMemcpyHostToDevice));   // offs has n + 2 >= 2 entries
         SCHK(rocprim::radix_sort_keys(nullptr, tb, vin, vsorted, (size_t)N, 0, 64, st));
-        SCHK(pool(9, tb ? tb : 8, &tmp));
+        SCHK(ctx_pool(ctx, SLOT_SETS_TMP, tb ? tb : 8, &tmp));
         SCHK(rocprim::radix_sort_keys(tmp, tb, vin, vsorted, (size_t)N, 0, 64, st));
     } else {
         SCHK(rocprim::segmented_radix_sort_keys(nullptr, tb, vin, vsorted, (unsigned)N, (unsigned)n, offs, offs + 1, 0, 64, st));
-        SCHK(pool(9, tb ? tb : 8, &tmp));
+        SCHK(ctx_pool(ctx, SLOT_SETS_TMP, tb ? tb : 8, &tmp));
         SCHK(rocprim::segmented_radix_sort_keys(tmp, tb, vin, vsorted, (unsigned)N, (unsigned)n, offs, offs + 1, 0, 64, st));
     }
     // 3. first occurrences that pass the filter -> compacted sets
-    SCHK(pool(6, N, (void **)&head));
-    SCHK(pool(7, N * 4, (void **)&keep));
-    SCHK(pool(8, (N + 1) * 8, (void **)&pos));
+    SCHK(ctx_pool(ctx, SLOT_SETS_HEAD, N, &head));
+    SCHK(ctx_pool(ctx, SLOT_SETS_KEEP, N * 4, &keep));
+    SCHK(ctx_pool(ctx, SLOT_SETS_POS, (N + 1) * 8, &pos));
     SCHK(hipMemsetAsync(head, 0, N, st));
-    hipLaunchKernelGGL(k_mark_heads, dim3(grid_of(ctx, n_sets, 256)), dim3(256), 0, st, set_offs, n_sets, head);
-    hipLaunchKernelGGL(k_flag_unique, dim3(grid_of(ctx, N, 256)), dim3(256), 0, st, vsorted, head, N, maxhash, keep);
+    hipLaunchKernelGGL(k_mark_heads, dim3(grid_for(ctx, n_sets, 256)), dim3(256), 0, st, set_offs, n_sets, head);
+    hipLaunchKernelGGL(k_flag_unique, dim3(grid_for(ctx, N, 256)), dim3(256), 0, st, vsorted, head, N, maxhash, keep);
     SCHK(hipGetLastError());
     // (the library's own three-kernel scan: rocprim::exclusive_scan over a transform iterator was 1.1 MB of the shared object)
     u64 *part2 = nullptr;
-    SCHK(pool(9, ((N + SCAN_CHUNK - 1) / SCAN_CHUNK + 2) * 8, (void **)&part2));
+    SCHK(ctx_pool(ctx, SLOT_SETS_TMP, scan_parts(N) * 8, &part2));
     SCHK(scan_counts(st, KeepOf{keep}, N, part2, pos, ctx->d_total + 1, (u64 *)nullptr));
     u64 M = 0;
     SCHK(hipMemcpyAsync(&M, ctx->d_total + 1, 8, hipMemcpyDeviceToHost, st));
     SCHK(hipStreamSynchronize(st));
-    hipLaunchKernelGGL(k_scatter_unique, dim3(grid_of(ctx, N, 256)), dim3(256), 0, st, vsorted, keep, pos, N, res->values);
-    hipLaunchKernelGGL(k_new_offsets, dim3(grid_of(ctx, n_sets + 1, 256)), dim3(256), 0, st, set_offs, pos, n_sets, N, M, res->offsets);
+    hipLaunchKernelGGL(k_scatter_unique, dim3(grid_for(ctx, N, 256)), dim3(256), 0, st, vsorted, keep, pos, N, res->values);
+    hipLaunchKernelGGL(k_new_offsets, dim3(grid_for(ctx, n_sets + 1, 256)), dim3(256), 0, st, set_offs, pos, n_sets, N, M, res->offsets);
     SCHK(hipGetLastError());
     if (counted) {  // every kept head's run length: the sorted array, the flags and the positions are all still here
         u64 *cpart = nullptr;
         SCHK(sets_grow_counts(res, M ? M : 1, reuse != nullptr));
-        SCHK(pool(40, sets_run_counts_parts(N) * 8, (void **)&cpart));
+        SCHK(ctx_pool(ctx, SLOT_COUNT_RUNS, sets_run_counts_parts(N) * 8, &cpart));
         SCHK(sets_run_counts(st, vsorted, keep, pos, N, maxhash, scale > 1, cpart, res->counts));
     }
     SCHK(hipStreamSynchronize(st));
@@ -816,15 +762,9 @@ extern "C" int bsk_sets_fetch_narrow(bsk_ctx *ctx, const bsk_sets *s, uint32_t *
     if (values && s->n_values > value_cap) return fail_arg(ctx, "bsk_sets_fetch_narrow: value_cap too small");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t need = (s->n_sets + 1) * 4;
-    if (ctx->tmp_cap[20] < need) {
-        (void)hipFree(ctx->tmp[20]);
-        ctx->tmp[20] = nullptr;
-        ctx->tmp_cap[20] = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->tmp[20], need + need / 4 + 256));
-        ctx->tmp_cap[20] = need + need / 4 + 256;
-    }
-    u32 *o32 = (u32 *)ctx->tmp[20];
-    hipLaunchKernelGGL(k_offsets_u32, dim3((unsigned)std::max<u64>(1, std::min<u64>((s->n_sets + 256) / 256, (u64)ctx->cus * 8))), dim3(256), 0, ctx->stream, s->offsets,
+    u32 *o32 = nullptr;
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_NARROW_OFFS, need, &o32));
+    hipLaunchKernelGGL(k_offsets_u32, dim3(grid_for(ctx, s->n_sets + 1, 256, 8)), dim3(256), 0, ctx->stream, s->offsets,
                        s->n_sets + 1, o32);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(offsets, o32, need, hipMemcpyDeviceToHost, ctx->stream));

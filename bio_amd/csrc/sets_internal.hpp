@@ -1,8 +1,11 @@
 // sets_internal.hpp -- what sets.hip shares with search.hip: the sets object behind bsk_sets, the library's own three-kernel exclusive
 // scan (rocprim::exclusive_scan over a transform iterator was 1.1 MB of the shared object) and the one 64-bit key sort sets.hip
-// instantiates.  Nothing here crosses the C ABI.
+// instantiates -- and, for setops.hip, counts.hip and compare.hip too, the host helpers around them (scan_parts, the capped grid, Carve).
+// Nothing here crosses the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "biosketch.h"
 #include "host_types.hpp"
@@ -29,7 +32,7 @@ u64 sets_run_counts_parts(u64 n) __attribute__((visibility("hidden")));
 hipError_t sets_run_counts(hipStream_t st, const u64 *v, const u32 *keep, const u64 *pos, u64 n, u64 maxhash, bool filt, u64 *part, u32 *counts)
     __attribute__((visibility("hidden")));
 // the sets' counts array, grow-only (reuse: with slack)
-hipError_t sets_grow_counts(bsk_sets *s, u64 n, bool slack) __attribute__((visibility("hidden")));
+static inline hipError_t sets_grow_counts(bsk_sets *s, u64 n, bool slack) { return grow_array(&s->counts, &s->c_counts, (n ? n : 1) * 4, slack); }
 // bsk_result_sets / _reuse / _counted (sets.hip)
 int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool counted, bsk_sets *reuse, bsk_sets **out) __attribute__((visibility("hidden")));
 
@@ -154,6 +157,28 @@ hipError_t scan_counts(hipStream_t st, F f, u64 n, u64 *part, u64 *out, u64 *tot
     if (nb) hipLaunchKernelGGL(k_scan_apply<F>, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, st, f, n, part, total_dev, out);
     else hipLaunchKernelGGL(k_scan_apply<F>, dim3(1), dim3(SCAN_BLOCK), 0, st, f, n, part, total_dev, out);
     return hipGetLastError();
+}
+inline u64 scan_parts(u64 n) { return (n + SCAN_CHUNK - 1) / SCAN_CHUNK + 2; }  // u64 of scan_counts' `part` for n numbers
+
+// ---- host-side helpers of the sets-side translation units ----
+// workgroups of `per_block` items, at most `blocks_per_cu` per CU and at least one
+inline unsigned grid_for(const bsk_ctx *ctx, u64 items, u64 per_block, u64 blocks_per_cu) {
+    const u64 g = (items + per_block - 1) / per_block;
+    return (unsigned)std::max<u64>(1, std::min<u64>(g, (u64)ctx->cus * blocks_per_cu));
+}
+// one pooled buffer carved into aligned pieces: add() every array, take Carve::bytes from the pool, then at() every piece
+struct Carve {
+    size_t bytes = 0;
+    template <class T>
+    size_t add(u64 n) {  // offset of an array of n T, 256-byte aligned
+        const size_t at = bytes;
+        bytes += ((n ? n : 1) * sizeof(T) + 255) & ~(size_t)255;
+        return at;
+    }
+};
+template <class T>
+T *at(void *base, size_t off) {
+    return reinterpret_cast<T *>(static_cast<char *>(base) + off);
 }
 
 }  // namespace

@@ -128,20 +128,7 @@ int sketch_tiled(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p_in, int c
     TileTab tt{nullptr, nullptr, nullptr, nullptr, nullptr};
     bsk_batch *tb = nullptr;
     bsk_result *tres = nullptr, *fin = nullptr;
-    // temporaries come from the context's grow-only pool (slot numbers below); the tile-level result is cached there too
-    auto pool = [&](int slot, size_t bytes, void **out) -> hipError_t {
-        if (ctx->tmp_cap[slot] < bytes) {
-            (void)hipFree(ctx->tmp[slot]);
-            ctx->tmp[slot] = nullptr;
-            ctx->tmp_cap[slot] = 0;
-            const size_t want = bytes + bytes / 4 + 256;
-            const hipError_t e = hipMalloc(&ctx->tmp[slot], want);
-            if (e != hipSuccess) return e;
-            ctx->tmp_cap[slot] = want;
-        }
-        *out = ctx->tmp[slot];
-        return hipSuccess;
-    };
+    // temporaries come from the context's grow-only pool (ctx_pool, SLOT_TILE_*); the tile-level result is cached there too
     bsk_result *old = nullptr;  // the caller's previous result (below)
     auto done = [&](int code) {
         if (tb) {  // the tile batch only borrowed its descriptor / flag arrays
@@ -189,7 +176,7 @@ int sketch_tiled(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p_in, int c
     const u32 nunits = (u32)((n + 63) / 64);
     int rc = ensure_scratch(ctx, std::max<u32>(nunits, 1), 0);
     if (rc != BSK_OK) return done(rc);
-    TCHK(pool(0, (n + 1) * 8, (void **)&tstart));
+    TCHK(ctx_pool(ctx, SLOT_TILE_START, (n + 1) * 8, &tstart));
     TCHK(hipMemsetAsync(tstart, 0, (n + 1) * 8, ctx->stream));
     // Without host round trips (round 6): the number of tiles is bounded on the host -- a sequence of L bases has at most L positions, so
     // at most L / tp + 1 tiles -- every array and grid is sized by the bound, the entries beyond the true count (on the device: tstart[n])
@@ -220,14 +207,14 @@ int sketch_tiled(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p_in, int c
     // 2. tile table + a batch whose "reads" are the tiles (aliases the words / bytes of b)
     const bool use_ascii = prot || b->n_nonacgt > 0;  // residues are bytes
     const size_t nta = nt ? nt : 1;
-    TCHK(pool(1, nta * 8, (void **)&tt.desc));
-    if (use_ascii) TCHK(pool(2, nta * 8, (void **)&tt.adesc));
-    TCHK(pool(3, nta * 4, (void **)&tt.seq));
-    TCHK(pool(4, nta * 8, (void **)&tt.shift));
-    TCHK(pool(5, nta * 8, (void **)&tt.keep));
+    TCHK(ctx_pool(ctx, SLOT_TILE_DESC, nta * 8, &tt.desc));
+    if (use_ascii) TCHK(ctx_pool(ctx, SLOT_TILE_ADESC, nta * 8, &tt.adesc));
+    TCHK(ctx_pool(ctx, SLOT_TILE_SEQ, nta * 4, &tt.seq));
+    TCHK(ctx_pool(ctx, SLOT_TILE_SHIFT, nta * 8, &tt.shift));
+    TCHK(ctx_pool(ctx, SLOT_TILE_KEEP, nta * 8, &tt.keep));
     u8 *tflags = nullptr;  // per tile: holds a non-ACGT letter (from the per-word bits of the batch); owned by tb later
     if (prot || (use_ascii && b->wbits)) {  // protein: all-zero flags = "the input-length rule was already applied" for every tile
-        TCHK(pool(6, nta, (void **)&tflags));
+        TCHK(ctx_pool(ctx, SLOT_TILE_FLAGS, nta, &tflags));
         TCHK(hipMemsetAsync(tflags, 0, nta, ctx->stream));
     }
     if (nt) {
@@ -361,8 +348,8 @@ int sketch_tiled(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p_in, int c
     }
     lap("kernels (+sizing)");
     // 4. per-sequence flags
-    TCHK(pool(7, (n ? n : 1) * 4, (void **)&sflags));
-    TCHK(pool(8, (n ? n : 1) * 8, (void **)&sbad));
+    TCHK(ctx_pool(ctx, SLOT_TILE_SEQ_FLAGS, (n ? n : 1) * 4, &sflags));
+    TCHK(ctx_pool(ctx, SLOT_TILE_SEQ_BAD, (n ? n : 1) * 8, &sbad));
     TCHK(hipMemsetAsync(sflags, 0, (n ? n : 1) * 4, ctx->stream));
     TCHK(hipMemsetAsync(sbad, 0xff, (n ? n : 1) * 8, ctx->stream));
     if (nt) {
@@ -411,7 +398,7 @@ int sketch_tiled(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p_in, int c
             fin->cap = fin->alloc_cap = cap;
         }
         lap("result arrays");
-        TCHK(pool(9, (nt + 1) * 8, (void **)&oexcl));
+        TCHK(ctx_pool(ctx, SLOT_TILE_EXCL, (nt + 1) * 8, &oexcl));
         TCHK(hipMemsetAsync(oexcl, 0, (nt + 1) * 8, ctx->stream));
         if (nt) {
             const u32 tunits = (u32)((nt + 63) / 64);

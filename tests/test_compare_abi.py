@@ -122,7 +122,7 @@ def test_library_exports_them(lib):
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.SO_PATH], capture_output=True, text=True, check=True).stdout
     exported = set(re.findall(r" T (bsk_\w+)", out))
     assert set(ENTRIES) <= exported
-    assert not [s for s in re.findall(r" [TW] (\S*(?:cmp_pool|cmp_grow|bottom_impl|compare_impl|k_cmp_tile|k_bt_gather)\S*)", out)]  # the helpers stay inside the library
+    assert not [s for s in re.findall(r" [TW] (\S*(?:ctx_pool|grow_array|bottom_impl|compare_impl|k_cmp_tile|k_bt_gather)\S*)", out)]  # the helpers stay inside the library
 
 
 def test_null_and_bad_arguments_without_a_device(lib):

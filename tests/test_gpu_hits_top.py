@@ -26,7 +26,7 @@ NS = (1, 2, 3, 16, 17, 64, 1024, 1025, 2048, 2049)
 
 @functools.lru_cache(None)
 def one_pass():
-    """how many items one pass of each capped grid of bsk_hits_top covers on device 0 (grid_for in search.hip)"""
+    """how many items one pass of each capped grid of bsk_hits_top covers on device 0 (grid_for in sets_internal.hpp)"""
     hip = C.CDLL("libamdhip64.so")
     hip.hipDeviceGetAttribute.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int]
     v = C.c_int()

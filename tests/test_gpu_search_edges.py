@@ -28,7 +28,7 @@ def _hip():
 
 
 def one_pass(engine):
-    """how many items one pass of each capped grid of bsk_index_search covers on device 0 (grid_for in search.hip)"""
+    """how many items one pass of each capped grid of bsk_index_search covers on device 0 (grid_for in sets_internal.hpp)"""
     v = C.c_int()
     assert _hip().hipDeviceGetAttribute(C.byref(v), 63, 0) == 0  # hipDeviceAttributeMultiprocessorCount
     cus = v.value
