@@ -236,6 +236,9 @@ void BskOpts::load() {
     no_ring = on("BSK_NO_RING");
     no_pkd = on("BSK_NO_PKD");
     no_side_early = on("BSK_NO_SIDE_EARLY");
+    pk_tail = env_u32("BSK_PK_TAIL", 1);  // at 10^8 x 150 bases any of 1..2 x 3..4 pays and they measure alike: the smallest (NOTEBOOK 4.3a)
+    pk_small = std::min(std::max(env_u32("BSK_PK_SMALL", 3), 3u), 8u);  // (fewer than three units would leave the request-ahead path)
+    pk_no_uniform = on("BSK_PK_NO_UNIFORM");  // A/B and tests: fixed-length batches on k_minimizer_pk's general form (descriptors, per-lane lengths)
     no_side_dense = on("BSK_NO_SIDE_DENSE");
     no_bin = on("BSK_NO_BIN");
     no_bin_early = on("BSK_NO_BIN_EARLY");
@@ -408,6 +411,7 @@ static int batch_from_ascii_impl(bsk_ctx *ctx, const uint8_t *bytes, const uint6
             if (hist) hist->add(L);
             w += (L + 15) / 16;
         }
+        if (b->uniform_len && !wide) b->word_stride = (maxlen + 15) / 16;  // (reads of one length, packed back to back: read r starts at word r * stride)
         delete b->hist;
         b->hist = hist;
         collect_odd(b, n, [&](u64 r) { return offsets[r + 1] - offsets[r]; });
@@ -490,11 +494,13 @@ static int batch_from_packed_impl(bsk_ctx *ctx, const uint32_t *words, uint64_t 
     HIPCHK(ctx, hipSetDevice(ctx->device));
     u32 maxlen = 0;
     u64 nb = 0;
-    bool uniform = true;
+    bool uniform = true, strided = true;  // strided: every read starts where the reads before it end, were they all as long as the first
+    const u64 wpr0 = n ? ((desc[0] & 0xffffffULL) + 15) / 16 : 0;
     std::unique_ptr<LenHist> hist;
     for (u64 r = 0; r < n; ++r) {
         u64 L = desc[r] & 0xffffffULL, w0 = desc[r] >> 24;
         if (w0 + (L + 15) / 16 > n_words) return fail_arg(ctx, "desc points outside words[]");
+        if (w0 != r * wpr0) strided = false;
         maxlen = std::max<u32>(maxlen, (u32)L);
         nb += L;
         if (L != (desc[0] & 0xffffffULL) && uniform) {  // the first read of another length: the histogram starts here (run_classed)
@@ -521,6 +527,7 @@ static int batch_from_packed_impl(bsk_ctx *ctx, const uint32_t *words, uint64_t 
     b->n_words = n_words;
     b->maxlen = maxlen;
     b->uniform_len = (n && uniform) ? maxlen : 0;
+    b->word_stride = (b->uniform_len && strided) ? (u32)wpr0 : 0;
     const u64 alloc_words = n_words + pad_words(maxlen);
     // device buffer of at least `need` bytes: the donor's if it is large enough (a streaming caller refills one batch object per
     // stream: hipFree / hipMalloc per chunk would synchronise the device), else a fresh one with 1/8 of slack
@@ -607,6 +614,7 @@ extern "C" int bsk_batch_synth(bsk_ctx *ctx, int alphabet, uint64_t n, uint32_t 
     hipError_t e = hipSuccess;
     if (alphabet == BSK_ALPHA_DNA) {
         const u32 wpr = (len + 15) / 16;
+        b->word_stride = wpr;  // (k_synth_dna: read r at word r * wpr)
         b->n_words = n * wpr;
         const u64 alloc_words = b->n_words + pad_words(len);
         if ((e = hipMalloc(&b->words, alloc_words * 4)) == hipSuccess && (e = hipMalloc(&b->desc, n * 8)) == hipSuccess &&

@@ -331,6 +331,7 @@ int class_build(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, const std
         v->maxlen = bk.hi;
         v->n_bases = pretend ? (u64)pretend * b->n : bk.bases;
         v->uniform_len = pretend;
+        v->word_stride = 0;  // (the view's reads keep their own lengths in memory: `pretend` is what the kernel makes of them)
         v->bdesc = bd;
         v->bflags = bf;
         v->c_bdesc = cbd;

@@ -23,6 +23,7 @@ int dense_minimizer_ascii_blocks_per_cu(int w);
 bool pk_minimizer_supported(int w);  // packed 32-bit window machine, w = 2..13 (kernels_pk.hpp)
 int pk_minimizer_blocks_per_cu(int w);
 u32 pk_minimizer_short_bases();
+bool pk_minimizer_uniform(bool long_reads, const KArgs &a);  // this launch takes the fixed-length form k_minimizer_pk<W, false, true>
 void pk_minimizer_launch(int w, bool long_reads, int grid, hipStream_t stream, const KArgs &a);
 void pk_minimizer_list_launch(int w, int grid, hipStream_t stream, const KArgs &a);  // the list pass alone: k_minimizer_dense<W, true>
 

@@ -14,7 +14,8 @@
 // Developer switches (DESIGN.md "Switches"): read from the environment ONCE, when the context is created, or again on
 // bsk_ctx_reload_options (the test suite flips them inside one process) -- never on the bsk_sketch path.
 struct BskOpts {
-    bool force_generic = false, no_mixed = false, no_dense = false, no_pk = false, no_ring = false, no_pkd = false, no_side_early = false, no_side_dense = false, ring = false, no_bin = false, no_bin_early = false, compact = false, no_spare = false, no_tiles = false, no_tile_cache = false, no_tile_defer = false, tile_dense = false, no_group_gather = false, timing = false,
+    u32 pk_tail = 1, pk_small = 3;  // k_minimizer_pk: the last pk_tail x (grid x 8) units of a launch of whole tickets go out as tickets of pk_small units (BSK_PK_TAIL, 0: none; BSK_PK_SMALL, 3..8)
+    bool force_generic = false, no_mixed = false, no_dense = false, no_pk = false, no_ring = false, no_pkd = false, no_side_early = false, pk_no_uniform = false, no_side_dense = false, ring = false, no_bin = false, no_bin_early = false, compact = false, no_spare = false, no_tiles = false, no_tile_cache = false, no_tile_defer = false, tile_dense = false, no_group_gather = false, timing = false,
          no_fused_translate = false, sets_no_small = false;
     int syn_margin = 2;
     u32 test_overflow = 0;   // BSK_TEST_OVERFLOW (tests): pretend an overflow flag once per call -- 1: in a timed re-run (BSK_RESIZE), 2: a class plan's part while sizing, 4: ... in a timed re-run (BSK_REPLAN_CLASS)
@@ -155,6 +156,7 @@ struct bsk_batch {
     u32 maxlen = 0;
     u32 side_maxlen = 0;   // class views: the longest read of the WHOLE batch (the ASCII side launch covers every flagged read, whatever its class); 0: maxlen
     u32 uniform_len = 0;  // != 0: every read has this length (synthetic batches)
+    u32 word_stride = 0;  // != 0: ... the batch is DNA and read r starts at word r * word_stride (= words per read): k_minimizer_pk needs no descriptors
     u32 *words = nullptr;
     u64 *desc = nullptr;   // NULL when a sequence has 2^24 bases or more: fw + llen then locate the sequences (tiled runs only)
     u64 *fw = nullptr;     // [n] first word

@@ -45,6 +45,7 @@ struct KArgs {
     u32 *ring_p;
     u32 ring_w;
     u32 uniform_len;  // != 0: every read has exactly this many bases (synthetic / fixed-length batches)
+    u32 uni_stride;   // != 0: ... and read r starts at word r * uni_stride (k_minimizer_pk's fixed-length form; 0 where a launch may not take it)
     u64 slab_read;  // per-sequence slab kernels (protein): tuples reserved per sequence
     u64 list_slab;  // k_minimizer_pkd: the slab of a LISTED read (its list pass runs with slab_read = this)
     u32 unit_rows;  // unit-row kernels (kernels_ring.hpp): rows of 64 tuples in a unit's slab
@@ -77,6 +78,7 @@ struct KArgs {
     u32 cls_lo, cls_hi, cls_pretend;  // class plans: see desc_len()
     u32 tk;          // units per ticket of the persistent-wave kernels (0: the kernel's own 4 or 8): a batch with fewer units than the grid has
                      // wavefronts x that number takes smaller tickets -- a pipeline chunk or a class plan's part is latency, not throughput
+    u32 tk_t0, tk_small;  // k_minimizer_pk: tickets from number tk_t0 on have tk_small units (0: none do) -- the end of a launch of whole tickets
     u32 list_grid;   // workgroups of the main launch = segments of the list of reads (list_append); the list pass may run with fewer
     u32 len_mask;    // 0xffffff, or 0xfff for binned descriptors
     u32 binned;

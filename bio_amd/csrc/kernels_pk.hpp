@@ -124,6 +124,26 @@ __device__ __forceinline__ PkWords pk_load_words(const u32 *p) {
                  : "v"(p));
     return r;
 }
+// The same with only the first nq (1..4, wave-uniform) of the four loads issued -- fixed-length batches, whose reads need wpr / 4 + 1 of
+// them.  The branches sit INSIDE the one asm statement: to the compiler all four registers are written here, whatever nq is, so no copy
+// of a register that was left out can appear between the loads and their wait.  What a register that was not loaded holds is never used
+// (PkMin::word2 reads the word of the base that enters and the one behind it: at most word wpr).
+__device__ __forceinline__ PkWords pk_load_words_n(const u32 *p, u32 nq) {
+    PkWords r;
+    asm volatile("global_load_dwordx4 %0, %4, off\n\t"
+                 "s_cmp_lt_u32 %5, 3\n\ts_cbranch_scc1 .Lpkw_low%=\n\t"
+                 "global_load_dwordx4 %1, %4, off offset:16\n\tglobal_load_dwordx4 %2, %4, off offset:32\n\t"
+                 "s_cmp_lt_u32 %5, 4\n\ts_cbranch_scc1 .Lpkw_end%=\n\t"
+                 "global_load_dwordx4 %3, %4, off offset:48\n\ts_branch .Lpkw_end%=\n"
+                 ".Lpkw_low%=:\n\t"
+                 "s_cmp_lt_u32 %5, 2\n\ts_cbranch_scc1 .Lpkw_end%=\n\t"
+                 "global_load_dwordx4 %1, %4, off offset:16\n"
+                 ".Lpkw_end%=:"
+                 : "=&v"(r.a), "=&v"(r.b), "=&v"(r.c), "=&v"(r.d)
+                 : "v"(p), "s"(nq)
+                 : "scc");
+    return r;
+}
 __device__ __forceinline__ u64 pk_load_u64(const u64 *p) {
     u64 r;
     asm volatile("global_load_dwordx2 %0, %1, off" : "=&v"(r) : "v"(p));
@@ -144,6 +164,9 @@ __device__ __forceinline__ void pk_ticket_async(u32 *ticket, u32 &t) {
 }
 __device__ __forceinline__ void pk_wait_loads(PkWords &p, u64 &d0, u32 &f, u32 &t) {
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(p.a), "+v"(p.b), "+v"(p.c), "+v"(p.d), "+v"(d0), "+v"(f), "+v"(t)::"memory");
+}
+__device__ __forceinline__ void pk_wait_loads(PkWords &p, u32 &f, u32 &t) {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(p.a), "+v"(p.b), "+v"(p.c), "+v"(p.d), "+v"(f), "+v"(t)::"memory");
 }
 __device__ __forceinline__ u32 pk_load_u8(const u8 *p) {
     u32 r;
@@ -680,8 +703,14 @@ __device__ __forceinline__ void pk_copyout(char *lds, int lane, u32 cnt, u32 exc
 #ifndef PK_TICKET
 #define PK_TICKET 8u  // units per ticket
 #endif
-template <int W, bool LONG>
+// UNI (never with LONG): a fixed-length batch whose read r starts at word r * uni_stride (KArgs::uni_stride; no class plan, no binned
+// view, no side launch: pk_minimizer_launch).  What the general form reads from a descriptor or reduces over the wave is a launch
+// constant here: no descriptor is loaded (a wave's first unit waits once, not twice, and unit N+1's words are requested from its
+// read number alone), length, window counts and the ragged blocks' window mask are scalars, and a read's words take wpr / 4 + 1
+// 16-byte loads instead of four.
+template <int W, bool LONG, bool UNI = false>
 __global__ __launch_bounds__(64, 2) void k_minimizer_pk(KArgs a) {  // two waves per SIMD (the LDS staging allows eight per CU): up to 256 VGPRs
+    static_assert(!(UNI && LONG), "k_minimizer_pk: the fixed-length form keeps the whole read in registers");
     typedef PkLds LY;
     __shared__ __attribute__((aligned(16))) char lds[LY::TOTAL];
     LDSQ char *const ldsq = (LDSQ char *)lds;
@@ -706,16 +735,26 @@ __global__ __launch_bounds__(64, 2) void k_minimizer_pk(KArgs a) {  // two waves
     const u32 lseg = a.fixcap / a.list_grid;  // this workgroup's segment of the list of reads for the exact machine (list_append)
     u32 lcur = 0;
     const u32 tku = a.tk ? a.tk : PK_TICKET;
+    // Tickets from number tk_t0 on have tk_small (>= 3: the request-ahead path holds) units instead of tku, so that the waves of the
+    // launch's last round end closer together (launch.hip; tk_small == 0: every ticket has tku units).
+    const u32 t0s = a.tk_small ? a.tk_t0 : 0xffffffffu, u0s = a.tk_small ? a.tk_t0 * tku : 0xffffffffu;
+    const u32 tsm = a.tk_small ? a.tk_small : tku;
+    auto ticket_unit = [&](u32 t) { return t < t0s ? t * tku : u0s + (t - t0s) * tsm; };  // a ticket's first unit
+    auto ticket_end = [&](u32 first) { return first + (first < u0s ? tku : tsm); };
+    // UNI: the windows of every read (0: the reads are SHORT) and the 16-byte loads its words take (word2 reads up to word wpr)
+    const u32 uL = a.uniform_len;
+    const u32 unk = (UNI && uL >= (u32)a.circ_ext && (uL - (u32)a.circ_ext) + 1u >= (u32)a.k + (u32)W) ? uL - (u32)a.k + 1u : 0u;
+    const u32 unq = a.uni_stride / 4u + 1u < 4u ? a.uni_stride / 4u + 1u : 4u;
     // The next ticket is requested at the start of the third-to-last unit of the current one and taken at that unit's wait, so its
     // first unit's descriptor and words enter the one-unit-ahead pipeline like any other unit's: only a wave's first unit loads its
     // own (have == false).  Tickets of one or two units take the next ticket when they end, as every ticket did before.
     const bool ahead = tku >= 3u;
     u32 tv = 0;       // lane 0: the returned ticket (in flight from the request to the wait)
     u32 nt = ~0u;     // first unit of the next ticket, once taken (>= nunits: there is none)
-    for (u32 unit = next_ticket(a.ticket, lane) * tku, uend = unit + tku; unit < a.nunits; ++unit, ({
+    for (u32 unit = ticket_unit(next_ticket(a.ticket, lane)), uend = ticket_end(unit); unit < a.nunits; ++unit, ({
              if (unit == uend) {
-                 unit = ahead ? nt : next_ticket(a.ticket, lane) * tku;
-                 uend = unit + tku;
+                 unit = ahead ? nt : ticket_unit(next_ticket(a.ticket, lane));
+                 uend = ticket_end(unit);
              }
          })) {
         const u64 r = (u64)unit * 64 + lane;
@@ -728,27 +767,50 @@ __global__ __launch_bounds__(64, 2) void k_minimizer_pk(KArgs a) {  // two waves
         // used): a value defined on one path only would reach its wait through a copy made BEFORE the wait, i.e. from registers whose
         // load the compiler does not know to be in flight.
         const u64 rmax = a.n - 1;
-        if (!have) {  // a wave's first unit, or the first of a ticket of one or two units: nothing was requested ahead
+        if constexpr (UNI) {
+            if (!have) {
+                pw_cur = pk_load_words_n(a.words + (r < rmax ? r : rmax) * (u64)a.uni_stride, unq);
+                pk_wait_loads(pw_cur);
+            }
+        } else if (!have) {  // a wave's first unit, or the first of a ticket of one or two units: nothing was requested ahead
             d_cur = pk_load_u64(a.desc + (r < rmax ? r : rmax));
             d_n1 = pk_load_u64(a.desc + (r + 64 < rmax ? r + 64 : rmax));
             pk_wait_loads(d_cur, d_n1);
             pw_cur = pk_load_words(a.words + (d_cur >> 24));
             pk_wait_loads(pw_cur);
         }
-        PkWords pw_n1 = pk_load_words(a.words + (d_n1 >> 24));
-        const u64 r2 = u2 * 64 + lane;
-        u64 d_n2 = pk_load_u64(a.desc + (r2 < rmax ? r2 : rmax));
+        PkWords pw_n1;
+        u64 d_n2 = 0;
+        if constexpr (UNI) {  // the next unit: this ticket's, or the next ticket's first (taken two units ago); without one, any read
+            const u64 r1 = ((!ahead || unit + 1u < uend) ? (u64)unit + 1u : (u64)nt) * 64 + lane;
+            pw_n1 = pk_load_words_n(a.words + (r1 < rmax ? r1 : rmax) * (u64)a.uni_stride, unq);
+        } else {
+            pw_n1 = pk_load_words(a.words + (d_n1 >> 24));
+            const u64 r2 = u2 * 64 + lane;
+            d_n2 = pk_load_u64(a.desc + (r2 < rmax ? r2 : rmax));
+        }
         // the read's input flags (batches packed from ASCII have them): a load after the copy-out would wait for its stores
         u32 rfl = pk_load_u8(a.rflags ? a.rflags + (r < rmax ? r : rmax) : reinterpret_cast<const u8 *>(a.desc));
         if (ask) pk_ticket_async(a.ticket, tv);
         const u64 d = d_cur;
         const PkWords pw = pw_cur;
-        const u64 off = d >> 24, L = desc_len(a, d);
-        const u64 ro = out_index(a, r, d);  // (length-binned batches: the read's own place in its chunk)
-        const bool ok = r < a.n && L >= (u64)a.circ_ext && (L - (u64)a.circ_ext) + 1 >= (u64)a.k + (u64)W;
-        const u32 nk = ok ? (u32)(L - a.k + 1) : 0u;
-        const u32 nk_max = wave_max_u32(nk);
-        const u32 nk_min = ~wave_max_u32(~(ok ? nk : 0xffffffffu));  // (over the lanes with a read)
+        u64 off, ro;
+        bool ok;
+        u32 nk, nk_max, nk_min;
+        if constexpr (UNI) {
+            off = 0;  // (only LONG reads its words from memory again)
+            ro = r;
+            ok = r < a.n && unk != 0u;
+            nk = nk_max = nk_min = unk;  // a scalar: so are the ragged blocks' window mask and its bit tests (a lane without a read stages on the spare row)
+        } else {
+            const u64 L = desc_len(a, d);
+            off = d >> 24;
+            ro = out_index(a, r, d);  // (length-binned batches: the read's own place in its chunk)
+            ok = r < a.n && L >= (u64)a.circ_ext && (L - (u64)a.circ_ext) + 1 >= (u64)a.k + (u64)W;
+            nk = ok ? (u32)(L - a.k + 1) : 0u;
+            nk_max = wave_max_u32(nk);
+            nk_min = ~wave_max_u32(~(ok ? nk : 0xffffffffu));  // (over the lanes with a read)
+        }
         u32 cnt = 0, tmin_lane = 0xffffffffu;
         if (nk_max) {
             tabs.write(ldsq);  // the previous copy-out's tables took their place
@@ -766,8 +828,10 @@ __global__ __launch_bounds__(64, 2) void k_minimizer_pk(KArgs a) {  // two waves
             if (ok) cnt = (lane < 32 ? pm.slot - col8 : top - pm.slot) / RB;
             tmin_lane = pm.tmin;
         }
-        pk_wait_loads(pw_n1, d_n2, rfl, tv);  // the next unit's words and descriptor (and the next ticket), requested a whole hashing phase ago, are in
-        if (ask) nt = (u32)__builtin_amdgcn_readfirstlane((int)tv) * tku;
+        // the next unit's words and descriptor (and the next ticket), requested a whole hashing phase ago, are in
+        if constexpr (UNI) pk_wait_loads(pw_n1, rfl, tv);
+        else pk_wait_loads(pw_n1, d_n2, rfl, tv);
+        if (ask) nt = ticket_unit((u32)__builtin_amdgcn_readfirstlane((int)tv));
         d_cur = d_n1;
         pw_cur = pw_n1;
         d_n1 = d_n2;
@@ -842,12 +906,18 @@ void pk_minimizer_list_launch(int w, int grid, hipStream_t stream, const KArgs &
         default: break;
     }
 }
+// The fixed-length form runs where the batch has a word stride (bsk_batch::word_stride) and the launch reads every read through its
+// own descriptor-free place: no class plan, no binned view, no subset -- the caller clears KArgs::uni_stride for a mixed batch.
+bool pk_minimizer_uniform(bool long_reads, const KArgs &a) { return !long_reads && a.uni_stride && a.uniform_len && !a.cls_hi && !a.binned && !a.subset; }
 void pk_minimizer_launch(int w, bool long_reads, int grid, hipStream_t stream, const KArgs &a) {
+    const bool uni = pk_minimizer_uniform(long_reads, a);
     switch (w) {
 #define X(WW)                                                                                               \
     case WW:                                                                                                \
         if (long_reads) {                                                                                   \
             hipLaunchKernelGGL((k_minimizer_pk<WW, true>), dim3(grid), dim3(64), 0, stream, a);             \
+        } else if (uni) {                                                                                   \
+            hipLaunchKernelGGL((k_minimizer_pk<WW, false, true>), dim3(grid), dim3(64), 0, stream, a);      \
         } else {                                                                                            \
             hipLaunchKernelGGL((k_minimizer_pk<WW, false>), dim3(grid), dim3(64), 0, stream, a);            \
         }                                                                                                   \

@@ -51,6 +51,8 @@ int launch(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, bsk_result *re
     a.pairs = b->pairs;
     a.circ_ext = circ_ext;
     a.uniform_len = b->uniform_len;
+    // k_minimizer_pk's fixed-length form: the main launch of a batch without a side launch (pk_minimizer_launch looks at the class plan and the binned view)
+    a.uni_stride = (b->alphabet == BSK_ALPHA_DNA && !pl.mixed && !ctx->opt.pk_no_uniform) ? b->word_stride : 0;
     a.refs = res->refs;
     a.status = res->status;
     a.hash = res->hash;
@@ -70,6 +72,11 @@ int launch(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, bsk_result *re
         if ((pl.which == K_MIN_PK || pl.which == K_MIN_PKD || pl.which == K_MIN_RING || pl.which == K_SYN_PK || pl.which == K_MIN_FAST || pl.which == K_MIN_DENSE || pl.which == K_SYN_FAST ||
              pl.which == K_PROT_MIN_FAST) && (u64)pl.nunits < waves * own)
             a.tk = (u32)std::max<u64>(1, ((u64)pl.nunits + waves - 1) / waves);  // (rounded up: one ticket per wavefront -- rounded down, 10^6 reads were 2 232 tickets of seven units on 2 048 wavefronts)
+        if (pl.which == K_MIN_PK && !a.tk && ctx->opt.pk_tail) {  // whole tickets: the last pk_tail rounds of the grid as smaller ones
+            const u64 region = std::min<u64>((u64)ctx->opt.pk_tail * waves * own, pl.nunits);
+            a.tk_t0 = (u32)(((u64)pl.nunits - region) / own);
+            a.tk_small = ctx->opt.pk_small;
+        }
     }
     if (cs && cs->masked) {  // class plan without a view: the kernel masks the other classes' reads itself (desc_len)
         a.cls_lo = cs->blo;
@@ -126,6 +133,7 @@ int launch(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, bsk_result *re
         sd.out_base = res->main_cap;
         sd.cap = res->cap;
         sd.uniform_len = 0;
+        sd.uni_stride = 0;
         sd.inplace = !kind_has_pos(p->kind);  // stream kinds: overwrite the read's own run, keep the layout contiguous
         sd.ticket = ctx->d_ticket + 2;
         sd.total = ctx->d_total + 2;
@@ -178,7 +186,12 @@ int launch(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, bsk_result *re
         case K_NT_P: hipLaunchKernelGGL(k_nthash_stream<0>, dim3(pl.grid), dim3(64), 0, ctx->stream, a); break;
         case K_NT_A: hipLaunchKernelGGL(k_nthash_stream<1>, dim3(pl.grid), dim3(64), 0, ctx->stream, a); break;
         case K_MIN_FAST: fast_minimizer_launch(pl.fast_w, pl.grid, ctx->stream, a); break;
-        case K_MIN_PK: pk_minimizer_launch(pl.fast_w, b->maxlen > pk_minimizer_short_bases(), pl.grid, ctx->stream, a); break;
+        case K_MIN_PK:
+            if (ctx->opt.timing)
+                fprintf(stderr, "[bsk] k_minimizer_pk: %s form, tk %u, tk_t0 %u, tk_small %u\n", pk_minimizer_uniform(b->maxlen > pk_minimizer_short_bases(), a) ? "fixed-length" : "general", a.tk, a.tk_t0,
+                        a.tk_small);
+            pk_minimizer_launch(pl.fast_w, b->maxlen > pk_minimizer_short_bases(), pl.grid, ctx->stream, a);
+            break;
         case K_MIN_RING: ring_minimizer_launch(pl.fast_w, b->maxlen > ring_minimizer_short_bases(), pl.grid, ctx->stream, a); break;
         case K_MIN_DENSE: dense_minimizer_launch(pl.fast_w, pl.grid, ctx->stream, a); break;
         case K_MIN_PKD: pkd_minimizer_launch(pl.fast_w, pl.grid, ctx->stream, a); break;
