@@ -69,7 +69,7 @@ extern "C" int bsk_ctx_create(int device, bsk_ctx **out) {
     ctx->opt.load();  // the developer switches: once per context
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc(&ctx->d_ticket, 32 * sizeof(u32)) != hipSuccess || hipMalloc(&ctx->d_total, 8 * sizeof(u64)) != hipSuccess ||
-        hipHostMalloc(&ctx->h_pinned, 8 * sizeof(u64)) != hipSuccess) {
+        hipHostMalloc(&ctx->h_pinned, bsk_ctx::PINNED_WORDS * sizeof(u64)) != hipSuccess) {
         bsk_ctx_destroy(ctx);
         return BSK_ERR_DEVICE;
     }
@@ -963,8 +963,7 @@ extern "C" int bsk_result_digest(bsk_ctx *ctx, const bsk_result *r, uint64_t *ch
                            ctx->d_total + 2);
     }
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, ctx->d_total, 8 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, read_back(ctx, ctx->d_total, 8));
     if (checksum) *checksum = ctx->h_pinned[0];
     if (n_tuples) *n_tuples = ctx->h_pinned[1];
     if (status_counts)
@@ -1110,8 +1109,7 @@ static int translate_batch(bsk_ctx *ctx, const bsk_batch *b, int table, int fram
             else hipLaunchKernelGGL(k_translate<0>, dim3(grid), dim3(64), 0, ctx->stream, a);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_pinned, ctx->d_total, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = read_back(ctx, ctx->d_total, 1);
         if (e != hipSuccess) {
             bsk_batch_destroy(t);
             return fail_hip(ctx, e, "translate");

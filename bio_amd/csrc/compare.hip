@@ -342,8 +342,7 @@ int bottom_impl(bsk_ctx *ctx, const bsk_sets *s, u64 n, bsk_sets *res) {
     u64 *tot = static_cast<u64 *>(bq), *part = tot + 8;
     HIPCHK(ctx, hipMemsetAsync(tot, 0, 64, st));
     HIPCHK(ctx, scan_counts(st, BtSize{s->offsets, n}, G, part, res->offsets, tot, (u64 *)nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, read_back(ctx, tot, 1));
     const u64 M = ctx->h_pinned[0];
     HIPCHK(ctx, grow_array(&res->values, &res->c_values, (M ? M : 1) * 8));
     if (s->counted) HIPCHK(ctx, sets_grow_counts(res, M ? M : 1, true));
@@ -398,8 +397,7 @@ int compare_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit, 
         hipLaunchKernelGGL(k_cmp_tile, dim3(grid), dim3(CMP_THREADS), 0, st, (const u64 *)a->offsets, (const u64 *)a->values, n_a, (const u64 *)b->offsets, (const u64 *)b->values, n_b,
                            lim, ntiles, tiles_x, res->shared, res->total, fig);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, fig, 24, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, read_back(ctx, fig, 3));
     for (int i = 0; i < 3; ++i) res->figures[i] = ctx->h_pinned[i];
     snprintf(res->plan, sizeof res->plan, "%s, %llu x %llu pairs in %llu tiles of %d x %d, windows of %d values, limit %llu",
              weighted ? "bsk_sets_compare_counted: k_cmp_tile_w" : "bsk_sets_compare: k_cmp_tile", (unsigned long long)n_a, (unsigned long long)n_b, (unsigned long long)ntiles,
@@ -425,18 +423,7 @@ extern "C" int bsk_sets_bottom(bsk_ctx *ctx, const bsk_sets *s, uint64_t n, bsk_
     if (s->ctx != ctx || (*out && (*out)->ctx != ctx)) return fail_arg(ctx, "bsk_sets_bottom: the sets belong to another context");
     if (*out == s) return fail_arg(ctx, "bsk_sets_bottom: *out is the input");
     if (n == 0) return fail_arg(ctx, "bsk_sets_bottom: n == 0");
-    bsk_sets *res = *out;
-    *out = nullptr;
-    if (!res) res = new (std::nothrow) bsk_sets();
-    if (!res) return BSK_ERR_NOMEM;
-    res->ctx = ctx;
-    const int rc = bottom_impl(ctx, s, n, res);
-    if (rc != BSK_OK) {
-        bsk_sets_release(res);
-        return rc;
-    }
-    *out = res;
-    return BSK_OK;
+    return take_over(ctx, out, bsk_sets_release, [&](bsk_sets *res, bool) { return bottom_impl(ctx, s, n, res); });
 }
 
 namespace {
@@ -445,28 +432,18 @@ int compare_entry(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, uint64_t l
     if (!ctx || !a || !b || !cmp) return fail_arg(ctx, weighted ? "bsk_sets_compare_counted: null argument" : "bsk_sets_compare: null argument");
     if (a->ctx != ctx || b->ctx != ctx || (*cmp && (*cmp)->ctx != ctx))
         return fail_arg(ctx, weighted ? "bsk_sets_compare_counted: the sets or the result belong to another context" : "bsk_sets_compare: the sets or the result belong to another context");
-    bsk_compare *res = *cmp;
-    *cmp = nullptr;
-    // both limits before anything is allocated (a == b holds its values once)
-    const u64 held = a == b ? a->n_values : a->n_values + b->n_values;
-    const bool many_values = a->n_values >= (1ULL << 32) || b->n_values >= (1ULL << 32) || held >= (1ULL << 32);
-    const bool many_cells = a->n_sets && b->n_sets > (1ULL << 31) / a->n_sets;
-    if (many_values || many_cells) {
-        bsk_compare_release(res);
-        if (weighted) ctx->err = many_values ? "bsk_sets_compare_counted: 2^32 values or more (split the sets)" : "bsk_sets_compare_counted: more than 2^31 cells (split the sets)";
-        else ctx->err = many_values ? "bsk_sets_compare: 2^32 values or more (split the sets)" : "bsk_sets_compare: more than 2^31 cells (split the sets)";
-        return BSK_ERR_UNSUPPORTED;
-    }
-    if (!res) res = new (std::nothrow) bsk_compare();
-    if (!res) return BSK_ERR_NOMEM;
-    res->ctx = ctx;
-    const int rc = compare_impl(ctx, a, b, limit, res, weighted);
-    if (rc != BSK_OK) {
-        bsk_compare_release(res);
-        return rc;
-    }
-    *cmp = res;
-    return BSK_OK;
+    return take_over(ctx, cmp, bsk_compare_release, [&](bsk_compare *res, bool) -> int {
+        // both limits after the slot is taken: a re-used object is released (a == b holds its values once)
+        const u64 held = a == b ? a->n_values : a->n_values + b->n_values;
+        const bool many_values = a->n_values >= (1ULL << 32) || b->n_values >= (1ULL << 32) || held >= (1ULL << 32);
+        const bool many_cells = a->n_sets && b->n_sets > (1ULL << 31) / a->n_sets;
+        if (many_values || many_cells) {
+            if (weighted) ctx->err = many_values ? "bsk_sets_compare_counted: 2^32 values or more (split the sets)" : "bsk_sets_compare_counted: more than 2^31 cells (split the sets)";
+            else ctx->err = many_values ? "bsk_sets_compare: 2^32 values or more (split the sets)" : "bsk_sets_compare: more than 2^31 cells (split the sets)";
+            return BSK_ERR_UNSUPPORTED;
+        }
+        return compare_impl(ctx, a, b, limit, res, weighted);
+    });
 }
 }  // namespace
 

@@ -183,8 +183,7 @@ int filter_impl(bsk_ctx *ctx, const bsk_sets *s, u32 lo, u32 hi, bsk_sets *res) 
     hipLaunchKernelGGL(k_fc_flags, dim3(ct_grid(ctx, N)), dim3(256), 0, st, s->counts, N, lo, hi, keep);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, scan_counts(st, KeepOf{keep}, N, part, pos, tot, (u64 *)nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, read_back(ctx, tot, 1));
     const u64 M = ctx->h_pinned[0];
     HIPCHK(ctx, grow_array(&res->values, &res->c_values, (M ? M : 1) * 8));
     HIPCHK(ctx, sets_grow_counts(res, M ? M : 1, true));
@@ -265,18 +264,7 @@ extern "C" int bsk_sets_filter_counts(bsk_ctx *ctx, const bsk_sets *s, uint32_t 
     if (*out == s) return fail_arg(ctx, "bsk_sets_filter_counts: *out is the input");
     if (!s->counted) return fail_arg(ctx, "bsk_sets_filter_counts: the sets are not counted");
     if (min_count == 0 || min_count > max_count) return fail_arg(ctx, "bsk_sets_filter_counts: min_count == 0 or min_count > max_count");
-    bsk_sets *res = *out;
-    *out = nullptr;
-    if (!res) res = new (std::nothrow) bsk_sets();
-    if (!res) return BSK_ERR_NOMEM;
-    res->ctx = ctx;
-    const int rc = filter_impl(ctx, s, min_count, max_count, res);
-    if (rc != BSK_OK) {
-        bsk_sets_release(res);
-        return rc;
-    }
-    *out = res;
-    return BSK_OK;
+    return take_over(ctx, out, bsk_sets_release, [&](bsk_sets *res, bool) { return filter_impl(ctx, s, min_count, max_count, res); });
 }
 
 extern "C" int bsk_sets_totals(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t count, uint64_t *totals) {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -79,7 +80,8 @@ struct bsk_ctx {
     u64 *d_ring_h = nullptr;  // runtime-w ring scratch
     u32 *d_ring_p = nullptr;
     size_t ring_cap = 0;  // entries
-    u64 *h_pinned = nullptr;  // [8] pinned host words for small read-backs
+    static constexpr unsigned PINNED_WORDS = 8;
+    u64 *h_pinned = nullptr;  // [PINNED_WORDS] pinned host words for small read-backs (read_back below)
     u8 *d_lut = nullptr;      // codon tables of `lut_table` (kernels_translate.hpp layout)
     int lut_table = 0;
     // grow-only temporaries of the entries (hipMalloc / hipFree of a tiled call's ten buffers cost more than its kernels)
@@ -278,4 +280,33 @@ static inline hipError_t ctx_pool(bsk_ctx *ctx, PoolSlot slot, size_t bytes, T *
     const hipError_t e = grow_array(&ctx->tmp[slot], &ctx->tmp_cap[slot], bytes);
     *out = static_cast<T *>(ctx->tmp[slot]);
     return e;
+}
+
+// A few device totals to the host: `n_words` u64 from `dev` to ctx->h_pinned[at ..] on the context's stream, then the synchronisation.  The
+// caller reads ctx->h_pinned[at .. at + n_words) when this returns hipSuccess.
+static inline hipError_t read_back(bsk_ctx *ctx, const u64 *dev, unsigned n_words, unsigned at = 0) {
+    if (at + n_words > bsk_ctx::PINNED_WORDS) return hipErrorInvalidValue;
+    const hipError_t e = hipMemcpyAsync(ctx->h_pinned + at, dev, n_words * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
+}
+
+// The in/out object slot of an entry (bsk_sets **out, bsk_hits **hits, bsk_compare **cmp): NULL, or an earlier result to re-use.  The
+// object is taken over for the call -- the slot is NULL while `run(res, reused)` works on it -- released when run fails, and stored back
+// when it returns BSK_OK.  What an entry checks BEFORE it calls this leaves the slot as it was; what it checks inside `run` releases a
+// re-used object (include/biosketch.h "The result slot" says which entry does which).
+template <class T, class F>
+static inline int take_over(bsk_ctx *ctx, T **slot, void (*release)(T *), F run) {
+    T *res = *slot;
+    *slot = nullptr;
+    const bool reused = res != nullptr;
+    if (!res) res = new (std::nothrow) T();
+    if (!res) return BSK_ERR_NOMEM;
+    res->ctx = ctx;
+    const int rc = run(res, reused);
+    if (rc != BSK_OK) {
+        release(res);
+        return rc;
+    }
+    *slot = res;
+    return BSK_OK;
 }

@@ -491,8 +491,7 @@ int run_planned(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, int circ_
     if (sizing && (pl.mixed || pl.slab || pl.which == K_NT_FAST || pl.which == K_PROT_HASH_FAST || pl.which == K_SIM_FAST || (ctx->cls && b == ctx->cls->view)) && b->n) {  // slab / line-padded kernels: sum the per-read counts once
         HIPCHK(ctx, hipMemsetAsync(ctx->d_total, 0, sizeof(u64), ctx->stream));
         hipLaunchKernelGGL(k_sum_counts, dim3(grid_for(ctx, b->n, 256)), dim3(256), 0, ctx->stream, (*result)->refs, b->n, ctx->d_total);
-        hipError_t e = hipMemcpyAsync(ctx->h_pinned, ctx->d_total, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        const hipError_t e = read_back(ctx, ctx->d_total, 1);
         if (e != hipSuccess) return cleanup(fail_hip(ctx, e, "bsk_sketch count"));
         (*result)->n_tuples = ctx->h_pinned[0];
     }

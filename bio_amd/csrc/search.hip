@@ -688,8 +688,7 @@ extern "C" int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index 
         hipLaunchKernelGGL(k_run_heads, dim3(grid_for(ctx, P, 256, 16)), dim3(256), 0, st, kout, P, flag);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, scan_counts(st, KeepOf{flag}, P, part, pos, tot, (u64 *)nullptr));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
+        HIPCHK(ctx, read_back(ctx, tot, 1));
         U = ctx->h_pinned[0];
     }
     int bits = 0;
@@ -709,8 +708,7 @@ extern "C" int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index 
     hipLaunchKernelGGL(k_ix_dir, dim3(grid_for(ctx, U + 1, 256, 16)), dim3(256), 0, st, ix->a->keys, U, bits, ix->a->dir);
     hipLaunchKernelGGL(k_ix_maxb, dim3(grid_for(ctx, nb, 256, 8)), dim3(256), 0, st, ix->a->dir, nb, tot + 1);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned + 1, tot + 1, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, read_back(ctx, tot + 1, 1, 1));
     ix->max_bucket = ctx->h_pinned[1];
     ix->device_bytes = (U ? U : 1) * 8 + (U + 1) * 4 + (P ? P : 1) * 4 + (nb + 1) * 4 + (T ? T : 1) * 4;
     *out = hold.release();
@@ -749,18 +747,7 @@ extern "C" int bsk_index_search(bsk_ctx *ctx, const bsk_index *ix, const bsk_set
         ctx->err = "bsk_index_search: 2^32 query sets or query values or more (split the queries)";
         return BSK_ERR_UNSUPPORTED;
     }
-    bsk_hits *res = *hits;
-    *hits = nullptr;
-    if (!res) res = new (std::nothrow) bsk_hits();
-    if (!res) return BSK_ERR_NOMEM;
-    res->ctx = ctx;
-    const int rc = search_impl(ctx, ix, queries, sp, res);
-    if (rc != BSK_OK) {
-        bsk_hits_release(res);
-        return rc;
-    }
-    *hits = res;
-    return BSK_OK;
+    return take_over(ctx, hits, bsk_hits_release, [&](bsk_hits *res, bool) { return search_impl(ctx, ix, queries, sp, res); });
 }
 
 static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, const bsk_search_params *sp, bsk_hits *res) {
@@ -794,8 +781,7 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
     HIPCHK(ctx, scan_counts(st, StageOf{qsum, T}, nq, part, stage_off, tot + 0, (u64 *)nullptr));
     HIPCHK(ctx, scan_counts(st, LargeOf{qsum, false}, nq, part, loff, tot + 1, (u64 *)nullptr));
     HIPCHK(ctx, scan_counts(st, LargeOf{qsum, true}, nq, part, lslot, tot + 2, (u64 *)nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 24, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, read_back(ctx, tot, 3));
     const u64 S = ctx->h_pinned[0], L = ctx->h_pinned[1], NL = ctx->h_pinned[2];
     void *bst = nullptr;
     HIPCHK(ctx, ctx_pool(ctx, SLOT_SEARCH_STAGE, (S ? S : 1) * 8, &bst));
@@ -840,8 +826,7 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
     }
     // hit offsets, then the move out of the staging spans
     HIPCHK(ctx, scan_counts(st, ArrayOf{hcnt}, nq, part, res->offsets, tot + 5, (u64 *)nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot + 5, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, read_back(ctx, tot + 5, 1));
     const u64 H = ctx->h_pinned[0];
     HIPCHK(ctx, grow_array(&res->target, &res->c_target, (H ? H : 1) * 4));
     HIPCHK(ctx, grow_array(&res->shared, &res->c_shared, (H ? H : 1) * 4));
@@ -864,18 +849,7 @@ extern "C" int bsk_hits_top(bsk_ctx *ctx, const bsk_hits *h, uint32_t n, bsk_hit
     if (h->ctx != ctx || (*top && (*top)->ctx != ctx)) return fail_arg(ctx, "bsk_hits_top: the hits belong to another context");
     if (*top == h) return fail_arg(ctx, "bsk_hits_top: *top is h itself");
     if (n == 0) return fail_arg(ctx, "bsk_hits_top: n == 0");
-    bsk_hits *res = *top;
-    *top = nullptr;
-    if (!res) res = new (std::nothrow) bsk_hits();
-    if (!res) return BSK_ERR_NOMEM;
-    res->ctx = ctx;
-    const int rc = top_impl(ctx, h, n, res);
-    if (rc != BSK_OK) {
-        bsk_hits_release(res);
-        return rc;
-    }
-    *top = res;
-    return BSK_OK;
+    return take_over(ctx, top, bsk_hits_release, [&](bsk_hits *res, bool) { return top_impl(ctx, h, n, res); });
 }
 
 static inline u32 bits_of(u64 x) { return x ? 64 - (u32)__builtin_clzll(x) : 0; }  // bits that hold 0 .. x
@@ -913,8 +887,7 @@ static int top_impl(bsk_ctx *ctx, const bsk_hits *h, u32 n, bsk_hits *res) {
             HIPCHK(ctx, hipGetLastError());
         }
     }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 56, hipMemcpyDeviceToHost, st));  // the one read-back
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, read_back(ctx, tot, 7));  // the one read-back
     const u64 H = ctx->h_pinned[0], L = ctx->h_pinned[1], NL = ctx->h_pinned[2], maxc = ctx->h_pinned[3], maxs = ctx->h_pinned[4], n_group = ctx->h_pinned[5],
               n_wave = ctx->h_pinned[6];
     HIPCHK(ctx, grow_array(&res->target, &res->c_target, (H ? H : 1) * 4));

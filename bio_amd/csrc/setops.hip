@@ -400,8 +400,7 @@ int op_impl(bsk_ctx *ctx, const SP sp, const u64 n, bool broadcast, const bsk_se
     HIPCHK(ctx, scan_counts(st, SoWaveOf<SP>{sp}, n, part, wslot, tot + 0, (u64 *)nullptr));
     HIPCHK(ctx, scan_counts(st, SoTilesOf<SP>{sp, false}, n, part, tfirst, tot + 1, (u64 *)nullptr));
     HIPCHK(ctx, scan_counts(st, SoTilesOf<SP>{sp, true}, n, part, tslot, tot + 2, (u64 *)nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 24, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, read_back(ctx, tot, 3));
     const u64 NW = ctx->h_pinned[0], NT = ctx->h_pinned[1], NTP = ctx->h_pinned[2], NG = n - NW - NTP;
     u64 *tcnt = nullptr, *tpos = nullptr, *part2 = nullptr;
     u32 *tpair = nullptr, *ta0 = nullptr;
@@ -431,8 +430,7 @@ int op_impl(bsk_ctx *ctx, const SP sp, const u64 n, bool broadcast, const bsk_se
     // 3. the tiles' places inside their pairs, the pairs' places in the output
     if (NT) HIPCHK(ctx, scan_counts(st, ArrayOf{tcnt}, NT, part2, tpos, tot + 3, (u64 *)nullptr));
     HIPCHK(ctx, scan_counts(st, SoPairCount{cnt, tfirst, tpos}, n, part, res->offsets, tot + 4, (u64 *)nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot + 4, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, read_back(ctx, tot + 4, 1));
     const u64 M = ctx->h_pinned[0];
     HIPCHK(ctx, grow_array(&res->values, &res->c_values, (M ? M : 1) * 8));
     if (COUNTED) HIPCHK(ctx, sets_grow_counts(res, M ? M : 1, true));
@@ -506,8 +504,7 @@ int reduce_impl(bsk_ctx *ctx, const bsk_sets *s, const uint64_t *group_offsets, 
     hipLaunchKernelGGL(k_rd_flags, dim3(grid_for(ctx, N, RD_CHUNK, 16)), dim3(256), 0, st, sorted, N, goff, gmem, G, min_members, keep);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, scan_counts(st, KeepOf{keep}, N, part, pos, tot, (u64 *)nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, tot, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));  // (the caller's group_offsets are not needed past this point)
+    HIPCHK(ctx, read_back(ctx, tot, 1));  // (the caller's group_offsets are not needed past this point)
     const u64 M = ctx->h_pinned[0];
     HIPCHK(ctx, grow_array(&res->values, &res->c_values, (M ? M : 1) * 8));
     if (M) hipLaunchKernelGGL(k_rd_scatter, dim3(grid_for(ctx, N, 256, 16)), dim3(256), 0, st, sorted, keep, pos, N, res->values);
@@ -519,23 +516,6 @@ int reduce_impl(bsk_ctx *ctx, const bsk_sets *s, const uint64_t *group_offsets, 
         snprintf(res->plan, sizeof res->plan, "bsk_sets_reduce: %llu groups, segmented sort + run test, every member", (unsigned long long)G);
     else
         snprintf(res->plan, sizeof res->plan, "bsk_sets_reduce: %llu groups, segmented sort + run test, >= %u members", (unsigned long long)G, min_members);
-    return BSK_OK;
-}
-
-// *out: NULL or an earlier result -- taken over for the call, released on failure
-template <class F>
-int into(bsk_ctx *ctx, bsk_sets **out, F run) {
-    bsk_sets *res = *out;
-    *out = nullptr;
-    if (!res) res = new (std::nothrow) bsk_sets();
-    if (!res) return BSK_ERR_NOMEM;
-    res->ctx = ctx;
-    const int rc = run(res);
-    if (rc != BSK_OK) {
-        bsk_sets_release(res);
-        return rc;
-    }
-    *out = res;
     return BSK_OK;
 }
 
@@ -553,7 +533,7 @@ extern "C" int bsk_sets_op(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, i
     }
     const u64 n = a->n_sets;
     const SoSpan sp{a->offsets, b->offsets, b->n_sets == n ? 1ull : 0ull};
-    return into(ctx, out, [&](bsk_sets *res) { return op_impl<SoSpan, false>(ctx, sp, n, sp.bstep == 0, a, b, op, res); });
+    return take_over(ctx, out, bsk_sets_release, [&](bsk_sets *res, bool) { return op_impl<SoSpan, false>(ctx, sp, n, sp.bstep == 0, a, b, op, res); });
 }
 
 // The counted algebra: BSK_COUNTOP_ADD / KEEP / DROP are union / intersection / difference on the values (the same numbers as
@@ -572,7 +552,7 @@ extern "C" int bsk_sets_op_counted(bsk_ctx *ctx, const bsk_sets *a, const bsk_se
         return BSK_ERR_UNSUPPORTED;
     }
     const SoSpanAB sp{a->offsets, b->offsets, a->n_sets == n ? 1ull : 0ull, b->n_sets == n ? 1ull : 0ull};
-    return into(ctx, out, [&](bsk_sets *res) { return op_impl<SoSpanAB, true>(ctx, sp, n, sp.astep == 0 || sp.bstep == 0, a, b, op, res); });
+    return take_over(ctx, out, bsk_sets_release, [&](bsk_sets *res, bool) { return op_impl<SoSpanAB, true>(ctx, sp, n, sp.astep == 0 || sp.bstep == 0, a, b, op, res); });
 }
 
 extern "C" int bsk_sets_reduce(bsk_ctx *ctx, const bsk_sets *s, const uint64_t *group_offsets, uint64_t n_groups, uint32_t min_members, bsk_sets **out) {
@@ -588,7 +568,7 @@ extern "C" int bsk_sets_reduce(bsk_ctx *ctx, const bsk_sets *s, const uint64_t *
         ctx->err = "bsk_sets_reduce: 2^32 sets, groups or values or more (split the sets)";
         return BSK_ERR_UNSUPPORTED;
     }
-    return into(ctx, out, [&](bsk_sets *res) { return reduce_impl(ctx, s, group_offsets, n_groups, min_members, res); });
+    return take_over(ctx, out, bsk_sets_release, [&](bsk_sets *res, bool) { return reduce_impl(ctx, s, group_offsets, n_groups, min_members, res); });
 }
 
 extern "C" int bsk_sets_plan(const bsk_sets *s, const char **plan, uint64_t n_by_path[3]) {

@@ -521,8 +521,7 @@ extern "C" int bsk_result_fetch_narrow(bsk_ctx *ctx, const bsk_result *r, uint64
                             ctx->d_total + 1, (u64 *)nullptr));
     u64 T = r->n_tuples;
     if (first != 0 || count != r->n) {  // (the whole result's count is known on the host: no round trip)
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, ctx->d_total + 1, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
+        HIPCHK(ctx, read_back(ctx, ctx->d_total + 1, 1));
         T = ctx->h_pinned[0];
     }
     if (n_tuples) *n_tuples = T;
@@ -545,8 +544,7 @@ extern "C" int bsk_result_fetch_narrow(bsk_ctx *ctx, const bsk_result *r, uint64
     if (status && count) HIPCHK(ctx, hipMemcpyAsync(status, r->status + first, count, hipMemcpyDeviceToHost, st));
     if (T) HIPCHK(ctx, hipMemcpyAsync(hash, oh, T * 8, hipMemcpyDeviceToHost, st));
     if (pos && T) HIPCHK(ctx, hipMemcpyAsync(pos, op, T * 2, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned + 1, ctx->d_total + 3, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, read_back(ctx, ctx->d_total + 3, 1, 1));
     if (pos && (ctx->h_pinned[1] & 1)) {
         ctx->err = "bsk_result_fetch_narrow: a position does not fit 15 bits (reads of 32 768 bases or more: use bsk_result_fetch)";
         return BSK_ERR_UNSUPPORTED;
@@ -563,43 +561,14 @@ extern "C" void bsk_sets_release(bsk_sets *s) {
     delete s;
 }
 
-extern "C" int bsk_result_sets(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets **out) {
-    return sets_build(ctx, r, scope, scale, false, nullptr, out);
-}
-// The same into an EXISTING sets object (*sets may be NULL the first time): its device arrays are kept and only grow, so a streaming
-// caller -- one chunk after the other through one object per stream -- allocates nothing in steady state (hipMalloc / hipFree
-// synchronise the whole device and would serialise the streams; bsk_batch_refill_ascii is the same idea for batches).  On error the
-// object is released and *sets is NULL.
-extern "C" int bsk_result_sets_reuse(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets **sets) {
-    if (!sets) return fail_arg(ctx, "bsk_result_sets_reuse: null argument");
-    bsk_sets *old = *sets;
-    if (old && old->ctx != ctx) return fail_arg(ctx, "bsk_result_sets_reuse: the sets belong to another context");
-    *sets = nullptr;
-    return sets_build(ctx, r, scope, scale, false, old, sets);
-}
-// The same with every kept value's run length (bsk_sets::counts): how often the value occurred in its scope.  Counted calls always take
-// the general path -- the run lengths fall out of its sorted array, its flags and its scan (counts.hip: sets_run_counts).
-extern "C" int bsk_result_sets_counted(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets **sets) {
-    if (!sets) return fail_arg(ctx, "bsk_result_sets_counted: null argument");
-    bsk_sets *old = *sets;
-    if (old && old->ctx != ctx) return fail_arg(ctx, "bsk_result_sets_counted: the sets belong to another context");
-    *sets = nullptr;
-    return sets_build(ctx, r, scope, scale, true, old, sets);
-}
-int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool counted, bsk_sets *reuse, bsk_sets **out) {
-    if (!ctx || !r || !out) {
-        if (reuse) bsk_sets_release(reuse);
-        return fail_arg(ctx, counted ? "bsk_result_sets_counted: null argument" : "bsk_result_sets: null argument");
-    }
-    *out = nullptr;
-    if (r->ctx != ctx || (scope != BSK_SETS_PER_SEQUENCE && scope != BSK_SETS_WHOLE_BATCH) || scale < 0) {
-        if (reuse) bsk_sets_release(reuse);
+namespace {
+// What the three entries below run on the object take_over hands them.  `reused`: an earlier result's arrays, which grow with slack (a
+// fresh object gets exactly what it needs).  Every failure in here releases the object and leaves the slot NULL.
+int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool counted, bsk_sets *res, bool reused) {
+    if (!ctx || !r) return fail_arg(ctx, counted ? "bsk_result_sets_counted: null argument" : "bsk_result_sets: null argument");
+    if (r->ctx != ctx || (scope != BSK_SETS_PER_SEQUENCE && scope != BSK_SETS_WHOLE_BATCH) || scale < 0)
         return fail_arg(ctx, r->ctx != ctx ? "bsk_result_sets: result belongs to another context" : scale < 0 ? "bsk_result_sets: bad scale" : "bsk_result_sets: bad scope");
-    }
-    if (hipSetDevice(ctx->device) != hipSuccess) {
-        if (reuse) bsk_sets_release(reuse);
-        return fail_arg(ctx, "bsk_result_sets: hipSetDevice");
-    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_arg(ctx, "bsk_result_sets: hipSetDevice");
     const u64 n = r->n;
     const u64 maxhash = scale > 1 ? ~0ULL / (u64)scale : ~0ULL;
     const u64 n_sets = scope == BSK_SETS_WHOLE_BATCH ? 1 : n;
@@ -608,122 +577,125 @@ int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool cou
     u8 *head = nullptr;
     u32 *keep = nullptr;
     void *tmp = nullptr;
-    bsk_sets *res = reuse;
-    auto done = [&](int code) {
-        if (code != BSK_OK && res) bsk_sets_release(res);
-        return code;
-    };
-#define SCHK(call)                                                  \
-    do {                                                            \
-        hipError_t e__ = (call);                                    \
-        if (e__ != hipSuccess) return done(fail_hip(ctx, e__, #call)); \
-    } while (0)
     // temporaries of every call come from the context's grow-only pool (hipMalloc / hipFree synchronise the device)
     // 1. where every sequence's values go in a dense copy: exclusive scan of the counts (+ the largest count)
     u64 *part = nullptr;
-    SCHK(ctx_pool(ctx, SLOT_SETS_OFFS, (n + 2) * 8, &offs));
-    SCHK(ctx_pool(ctx, SLOT_SETS_PART, scan_parts(n) * 8, &part));
-    SCHK(hipMemsetAsync(ctx->d_total, 0, 16, st));  // [0] largest count, [1] total
-    SCHK(scan_counts(st, CountOf{r->refs, r->wfirst, r->wcount}, n, part, offs, ctx->d_total + 1, ctx->d_total));
-    u64 N = 0, max_count = 0;
-    SCHK(hipMemcpyAsync(&N, ctx->d_total + 1, 8, hipMemcpyDeviceToHost, st));
-    SCHK(hipMemcpyAsync(&max_count, ctx->d_total, 8, hipMemcpyDeviceToHost, st));
-    SCHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SETS_OFFS, (n + 2) * 8, &offs));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SETS_PART, scan_parts(n) * 8, &part));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_total, 0, 16, st));  // [0] largest count, [1] total
+    HIPCHK(ctx, scan_counts(st, CountOf{r->refs, r->wfirst, r->wcount}, n, part, offs, ctx->d_total + 1, ctx->d_total));
+    HIPCHK(ctx, read_back(ctx, ctx->d_total, 2));
+    const u64 max_count = ctx->h_pinned[0], N = ctx->h_pinned[1];
     size_t tb = 0;
     if (N >= (1ULL << 32)) {
         ctx->err = "bsk_result_sets: more than 2^32 values in one call (split the batch)";
-        return done(BSK_ERR_UNSUPPORTED);
+        return BSK_ERR_UNSUPPORTED;
     }
-    if (!res) res = new (std::nothrow) bsk_sets();
-    if (!res) return done(BSK_ERR_NOMEM);
-    res->ctx = ctx;
     res->n_sets = n_sets;
     res->n_values = 0;
     res->plan[0] = 0;  // (a re-used object may have been a set operation's result: bsk_sets_plan describes those only)
     res->by_path[0] = res->by_path[1] = res->by_path[2] = 0;
     res->counted = false;  // (a re-used counted object keeps its counts array, not its counts)
-    SCHK(grow_array(&res->offsets, &res->c_offsets, (n_sets + 1) * 8, reuse != nullptr));  // the sets' own arrays: grow-only; a fresh object gets exactly what it needs
-    SCHK(grow_array(&res->values, &res->c_values, (N ? N : 1) * 8, reuse != nullptr));
+    HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (n_sets + 1) * 8, reused));  // the sets' own arrays: grow-only; a fresh object gets exactly what it needs
+    HIPCHK(ctx, grow_array(&res->values, &res->c_values, (N ? N : 1) * 8, reused));
     if (N == 0) {
-        SCHK(hipMemsetAsync(res->offsets, 0, (n_sets + 1) * 8, st));
-        if (counted) SCHK(sets_grow_counts(res, 1, reuse != nullptr));
-        SCHK(hipStreamSynchronize(st));
+        HIPCHK(ctx, hipMemsetAsync(res->offsets, 0, (n_sets + 1) * 8, st));
+        if (counted) HIPCHK(ctx, sets_grow_counts(res, 1, reused));
+        HIPCHK(ctx, hipStreamSynchronize(st));
         res->counted = counted;
-        *out = res;
-        return done(BSK_OK);
+        return BSK_OK;
     }
     if (scope == BSK_SETS_PER_SEQUENCE && max_count <= SMALL_CAP && !ctx->opt.sets_no_small && !counted) {
         // short reads: one sequence per row of 16 lanes, bitonic network over DPP moves (k_sets_rows)
         u64 *ucount = nullptr, *dense = nullptr;
-        SCHK(ctx_pool(ctx, SLOT_SETS_VALUES, N * 8, &dense));          // the sequences' distinct values at their input offsets
-        SCHK(ctx_pool(ctx, SLOT_SETS_UCOUNT, (n + 2) * 8, &ucount));
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_SETS_VALUES, N * 8, &dense));          // the sequences' distinct values at their input offsets
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_SETS_UCOUNT, (n + 2) * 8, &ucount));
         const unsigned sgrid = grid_for(ctx, n, 16, 32);
         hipLaunchKernelGGL(k_sets_rows, dim3(sgrid), dim3(256), 0, st, r->hash, r->refs, r->wfirst, r->wcount, offs, n, maxhash, dense, ucount);
-        SCHK(hipGetLastError());
-        SCHK(scan_counts(st, ArrayOf{ucount}, n, part, res->offsets, ctx->d_total + 1, (u64 *)nullptr));
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, scan_counts(st, ArrayOf{ucount}, n, part, res->offsets, ctx->d_total + 1, (u64 *)nullptr));
         if (!ctx->opt.no_group_gather)
             hipLaunchKernelGGL(k_move_groups, dim3(grid_for(ctx, n, 256, 16)), dim3(256), 0, st, dense, offs,
                                res->offsets, ucount, n, res->values);
         else
             hipLaunchKernelGGL(k_move_seqs, dim3(grid_for(ctx, n, 8, 32)), dim3(256), 0, st, dense, offs, res->offsets,
                                ucount, n, res->values);
-        SCHK(hipGetLastError());
-        u64 M = 0;
-        SCHK(hipMemcpyAsync(&M, ctx->d_total + 1, 8, hipMemcpyDeviceToHost, st));
-        SCHK(hipStreamSynchronize(st));
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, read_back(ctx, ctx->d_total + 1, 1));
+        const u64 M = ctx->h_pinned[0];
         res->n_values = M;
-        *out = res;
-        return done(BSK_OK);
+        return BSK_OK;
     }
-    SCHK(ctx_pool(ctx, SLOT_SETS_VALUES, N * 8, &vin));  // (all temporaries are pooled: in a process that has already cycled ~100 GB of batches a
-    SCHK(ctx_pool(ctx, SLOT_SETS_SORTED, N * 8, &vsorted));  //  hipMalloc / hipFree of these buffers cost 70-200 ms per call against 10-18 ms of kernels)
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SETS_VALUES, N * 8, &vin));  // (all temporaries are pooled: in a process that has already cycled ~100 GB of batches a
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SETS_SORTED, N * 8, &vsorted));  //  hipMalloc / hipFree of these buffers cost 70-200 ms per call against 10-18 ms of kernels)
     hipLaunchKernelGGL(k_gather_values, dim3(grid_for(ctx, n * 16, 256)), dim3(256), 0, st, r->hash, r->refs, r->wfirst, r->wcount, offs, n,
                        maxhash, vin);
-    SCHK(hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
     // 2. sort inside every set
     u64 *set_offs = offs;  // per-sequence scope: the gather offsets ARE the segment offsets
     if (scope == BSK_SETS_WHOLE_BATCH) {
         const u64 two[2] = {0, N};
-        SCHK(hipStreamSynchronize(st));                           // the gather above still reads offs
-        SCHK(hipMemcpy(offs, two, 16, hipMemcpyHostToDevice));   // offs has n + 2 >= 2 entries
-        SCHK(rocprim::radix_sort_keys(nullptr, tb, vin, vsorted, (size_t)N, 0, 64, st));
-        SCHK(ctx_pool(ctx, SLOT_SETS_TMP, tb ? tb : 8, &tmp));
-        SCHK(rocprim::radix_sort_keys(tmp, tb, vin, vsorted, (size_t)N, 0, 64, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));                           // the gather above still reads offs
+        HIPCHK(ctx, hipMemcpy(offs, two, 16, hipMemcpyHostToDevice));   // offs has n + 2 >= 2 entries
+        HIPCHK(ctx, rocprim::radix_sort_keys(nullptr, tb, vin, vsorted, (size_t)N, 0, 64, st));
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_SETS_TMP, tb ? tb : 8, &tmp));
+        HIPCHK(ctx, rocprim::radix_sort_keys(tmp, tb, vin, vsorted, (size_t)N, 0, 64, st));
     } else {
-        SCHK(rocprim::segmented_radix_sort_keys(nullptr, tb, vin, vsorted, (unsigned)N, (unsigned)n, offs, offs + 1, 0, 64, st));
-        SCHK(ctx_pool(ctx, SLOT_SETS_TMP, tb ? tb : 8, &tmp));
-        SCHK(rocprim::segmented_radix_sort_keys(tmp, tb, vin, vsorted, (unsigned)N, (unsigned)n, offs, offs + 1, 0, 64, st));
+        HIPCHK(ctx, rocprim::segmented_radix_sort_keys(nullptr, tb, vin, vsorted, (unsigned)N, (unsigned)n, offs, offs + 1, 0, 64, st));
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_SETS_TMP, tb ? tb : 8, &tmp));
+        HIPCHK(ctx, rocprim::segmented_radix_sort_keys(tmp, tb, vin, vsorted, (unsigned)N, (unsigned)n, offs, offs + 1, 0, 64, st));
     }
     // 3. first occurrences that pass the filter -> compacted sets
-    SCHK(ctx_pool(ctx, SLOT_SETS_HEAD, N, &head));
-    SCHK(ctx_pool(ctx, SLOT_SETS_KEEP, N * 4, &keep));
-    SCHK(ctx_pool(ctx, SLOT_SETS_POS, (N + 1) * 8, &pos));
-    SCHK(hipMemsetAsync(head, 0, N, st));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SETS_HEAD, N, &head));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SETS_KEEP, N * 4, &keep));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SETS_POS, (N + 1) * 8, &pos));
+    HIPCHK(ctx, hipMemsetAsync(head, 0, N, st));
     hipLaunchKernelGGL(k_mark_heads, dim3(grid_for(ctx, n_sets, 256)), dim3(256), 0, st, set_offs, n_sets, head);
     hipLaunchKernelGGL(k_flag_unique, dim3(grid_for(ctx, N, 256)), dim3(256), 0, st, vsorted, head, N, maxhash, keep);
-    SCHK(hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
     // (the library's own three-kernel scan: rocprim::exclusive_scan over a transform iterator was 1.1 MB of the shared object)
     u64 *part2 = nullptr;
-    SCHK(ctx_pool(ctx, SLOT_SETS_TMP, scan_parts(N) * 8, &part2));
-    SCHK(scan_counts(st, KeepOf{keep}, N, part2, pos, ctx->d_total + 1, (u64 *)nullptr));
-    u64 M = 0;
-    SCHK(hipMemcpyAsync(&M, ctx->d_total + 1, 8, hipMemcpyDeviceToHost, st));
-    SCHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SETS_TMP, scan_parts(N) * 8, &part2));
+    HIPCHK(ctx, scan_counts(st, KeepOf{keep}, N, part2, pos, ctx->d_total + 1, (u64 *)nullptr));
+    HIPCHK(ctx, read_back(ctx, ctx->d_total + 1, 1));
+    const u64 M = ctx->h_pinned[0];
     hipLaunchKernelGGL(k_scatter_unique, dim3(grid_for(ctx, N, 256)), dim3(256), 0, st, vsorted, keep, pos, N, res->values);
     hipLaunchKernelGGL(k_new_offsets, dim3(grid_for(ctx, n_sets + 1, 256)), dim3(256), 0, st, set_offs, pos, n_sets, N, M, res->offsets);
-    SCHK(hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
     if (counted) {  // every kept head's run length: the sorted array, the flags and the positions are all still here
         u64 *cpart = nullptr;
-        SCHK(sets_grow_counts(res, M ? M : 1, reuse != nullptr));
-        SCHK(ctx_pool(ctx, SLOT_COUNT_RUNS, sets_run_counts_parts(N) * 8, &cpart));
-        SCHK(sets_run_counts(st, vsorted, keep, pos, N, maxhash, scale > 1, cpart, res->counts));
+        HIPCHK(ctx, sets_grow_counts(res, M ? M : 1, reused));
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_COUNT_RUNS, sets_run_counts_parts(N) * 8, &cpart));
+        HIPCHK(ctx, sets_run_counts(st, vsorted, keep, pos, N, maxhash, scale > 1, cpart, res->counts));
     }
-    SCHK(hipStreamSynchronize(st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     res->n_values = M;
     res->counted = counted;
-#undef SCHK
-    *out = res;
-    return done(BSK_OK);
+    return BSK_OK;
+}
+
+}  // namespace
+
+extern "C" int bsk_result_sets(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets **out) {
+    if (!ctx || !r || !out) return fail_arg(ctx, "bsk_result_sets: null argument");
+    *out = nullptr;  // (write-only here: what the slot held is not looked at)
+    return take_over(ctx, out, bsk_sets_release, [&](bsk_sets *res, bool reused) { return sets_build(ctx, r, scope, scale, false, res, reused); });
+}
+// The same into an EXISTING sets object (*sets may be NULL the first time): its device arrays are kept and only grow, so a streaming
+// caller -- one chunk after the other through one object per stream -- allocates nothing in steady state (hipMalloc / hipFree
+// synchronise the whole device and would serialise the streams; bsk_batch_refill_ascii is the same idea for batches).  Sets of another
+// context are refused and stay in the slot; on every other error the object is released and *sets is NULL.
+extern "C" int bsk_result_sets_reuse(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets **sets) {
+    if (!sets) return fail_arg(ctx, "bsk_result_sets_reuse: null argument");
+    if (*sets && (*sets)->ctx != ctx) return fail_arg(ctx, "bsk_result_sets_reuse: the sets belong to another context");
+    return take_over(ctx, sets, bsk_sets_release, [&](bsk_sets *res, bool reused) { return sets_build(ctx, r, scope, scale, false, res, reused); });
+}
+// The same with every kept value's run length (bsk_sets::counts): how often the value occurred in its scope.  Counted calls always take
+// the general path -- the run lengths fall out of its sorted array, its flags and its scan (counts.hip: sets_run_counts).
+extern "C" int bsk_result_sets_counted(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets **sets) {
+    if (!sets) return fail_arg(ctx, "bsk_result_sets_counted: null argument");
+    if (*sets && (*sets)->ctx != ctx) return fail_arg(ctx, "bsk_result_sets_counted: the sets belong to another context");
+    return take_over(ctx, sets, bsk_sets_release, [&](bsk_sets *res, bool reused) { return sets_build(ctx, r, scope, scale, true, res, reused); });
 }
 
 hipError_t sets_sort_u64(void *tmp, size_t &tmp_bytes, u64 *in, u64 *out, size_t n, unsigned begin_bit, unsigned end_bit, hipStream_t st) {

@@ -33,8 +33,6 @@ hipError_t sets_run_counts(hipStream_t st, const u64 *v, const u32 *keep, const 
     __attribute__((visibility("hidden")));
 // the sets' counts array, grow-only (reuse: with slack)
 static inline hipError_t sets_grow_counts(bsk_sets *s, u64 n, bool slack) { return grow_array(&s->counts, &s->c_counts, (n ? n : 1) * 4, slack); }
-// bsk_result_sets / _reuse / _counted (sets.hip)
-int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool counted, bsk_sets *reuse, bsk_sets **out) __attribute__((visibility("hidden")));
 
 // rocprim::radix_sort_keys<u64> over bits [begin_bit, end_bit) on `st` (sets.hip: the instantiation its whole-batch sets use).
 // tmp == nullptr: *tmp_bytes receives the temporary storage it needs.

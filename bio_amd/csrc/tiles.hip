@@ -198,8 +198,7 @@ int sketch_tiled(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p_in, int c
         if (defer) {
             nt = b->n_bases / geo.tp + n;
         } else {
-            TCHK(hipMemcpyAsync(ctx->h_pinned, tstart + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-            TCHK(hipStreamSynchronize(ctx->stream));
+            TCHK(read_back(ctx, tstart + n, 1));
             nt = ctx->h_pinned[0];
         }
     }

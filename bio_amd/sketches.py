@@ -92,7 +92,45 @@ def NewSeq(alphabet: Alphabet, seq) -> Tuple[Seq, None]:
 
 
 # ---- engine ---------------------------------------------------------------------------------------
-class Batch:
+class _Owner:
+    """Owns one library handle: close() hands it to the library's release function once, and so does garbage collection."""
+
+    _release = ""  # the release function's name
+    _slot = "h"    # the attribute that holds the handle
+
+    def close(self):
+        h = getattr(self, self._slot, None)  # (None as well when the constructor failed before it had a handle)
+        if h:
+            getattr((getattr(self, "eng", None) or self).lib, self._release)(h)
+            setattr(self, self._slot, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _take_over(eng: "Engine", into, call):
+    """call(byref(slot)) with the handle of `into` -- None, or any owner with an .h to re-use -- in the slot -> the slot's handle.
+    into.h follows the slot before the return code raises: kept where the library refuses the call before it takes the object
+    over, None where it released it (include/biosketch.h, "The result slot")."""
+    h = into.h if into is not None and into.h else C.c_void_p()
+    rc = call(C.byref(h))
+    if into is not None:
+        into.h = h if h.value else None
+    eng._chk(rc)
+    return h
+
+
+def _chk_pipeline(lib, what: str, rc: int):
+    if rc != L.OK:
+        raise _SENTINELS.get(rc) or DeviceError(f"{what}: {lib.bsk_err_name(rc).decode()}")
+
+
+class Batch(_Owner):
+    _release = "bsk_batch_destroy"
+
     def __init__(self, eng: "Engine", handle):
         self.eng, self.h = eng, handle
 
@@ -118,20 +156,11 @@ class Batch:
         self.eng._chk(self.eng.lib.bsk_batch_translate(self.eng.ctx, self.h, codon_table, frame, C.byref(h)))
         return Batch(self.eng, h)
 
-    def close(self):
-        if self.h:
-            self.eng.lib.bsk_batch_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BatchResult:
+class BatchResult(_Owner):
     """Device-resident CSR result of one bsk_sketch call."""
+
+    _release = "bsk_result_release"
 
     def __init__(self, eng: "Engine", handle, params: L.Params):
         self.eng, self.h, self.params = eng, handle, params
@@ -215,12 +244,9 @@ class BatchResult:
     def counted_sets(self, whole_batch: bool = False, scale: int = 1, into: Optional["Sets"] = None) -> "Sets":
         """device_sets() with every value's abundance (bsk_result_sets_counted): counts[i] = how many tuples of the set's scope hold
         values[i].  into: a Sets of this engine to re-use (its device arrays are kept and only grow)."""
-        h = into.h if into is not None and into.h else C.c_void_p()
         self.eng._opts()
-        rc = self.eng.lib.bsk_result_sets_counted(self.eng.ctx, self.h, L.SETS_WHOLE_BATCH if whole_batch else L.SETS_PER_SEQUENCE, scale, C.byref(h))
-        if into is not None:
-            into.h = h if h.value else None
-        self.eng._chk(rc)
+        scope = L.SETS_WHOLE_BATCH if whole_batch else L.SETS_PER_SEQUENCE
+        h = _take_over(self.eng, into, lambda out: self.eng.lib.bsk_result_sets_counted(self.eng.ctx, self.h, scope, scale, out))
         return into if into is not None else Sets(self.eng, h)
 
     def compact(self):
@@ -249,20 +275,11 @@ class BatchResult:
         a, b = int(offs[i]), int(offs[i + 1])
         return int(status[i]), h[a:b], (p[a:b] if p is not None else None)
 
-    def close(self):
-        if self.h:
-            self.eng.lib.bsk_result_release(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Sets:
+class Sets(_Owner):
     """Device-resident sorted distinct value sets (bsk_sets): offsets[n_sets+1] and values[] stay on the device until close()."""
+
+    _release = "bsk_sets_release"
 
     def __init__(self, eng: "Engine", handle):
         self.eng, self.h = eng, handle
@@ -301,14 +318,8 @@ class Sets:
 
     # -- set algebra (bsk_sets_op / bsk_sets_reduce): the result is a Sets of the same engine, left on the device
     def _into(self, into: Optional["Sets"], call) -> "Sets":
-        h = into.h if into is not None and into.h else C.c_void_p()
-        rc = call(C.byref(h))
-        if into is not None:
-            into.h = h if h.value else None  # (kept on an argument error, released by the library on any other)
-        self.eng._chk(rc)
-        if into is None:
-            into = Sets(self.eng, h)
-        return into
+        h = _take_over(self.eng, into, call)
+        return into if into is not None else Sets(self.eng, h)
 
     def op(self, other: "Sets", op: int, into: Optional["Sets"] = None) -> "Sets":
         """Set i of the result is self[i] op other[i]; an `other` of exactly one set is combined with every set of self (bsk_sets_op).
@@ -398,11 +409,7 @@ class Sets:
         (0: all of them) and how many of those both sets hold (bsk_sets_compare).  limit 0 gives the exact Jaccard, limit n the
         Mash estimator of bottom-n sketches.  reuse: the Compare of an earlier call on this engine, whose device arrays are kept."""
         other = self if other is None else other
-        h = reuse.h if reuse is not None and reuse.h else C.c_void_p()
-        rc = self.eng.lib.bsk_sets_compare(self.eng.ctx, self.h, other.h, limit, C.byref(h))
-        if reuse is not None:
-            reuse.h = h if h.value else None  # (kept on an argument error, released by the library on any other)
-        self.eng._chk(rc)
+        h = _take_over(self.eng, reuse, lambda out: self.eng.lib.bsk_sets_compare(self.eng.ctx, self.h, other.h, limit, out))
         res = reuse if reuse is not None else Compare(self.eng)
         res._bind(h, np.diff(self.offsets()))
         return res
@@ -412,11 +419,7 @@ class Sets:
         both sets hold dot = the sum of the products of the two counts (u64, saturating) and min_sum = the sum of their minima.
         Sets without counts count 1 for every value.  The Compare keeps both operands for its norms (cosine() and its kin)."""
         other = self if other is None else other
-        h = reuse.h if reuse is not None and reuse.h else C.c_void_p()
-        rc = self.eng.lib.bsk_sets_compare_counted(self.eng.ctx, self.h, other.h, limit, C.byref(h))
-        if reuse is not None:
-            reuse.h = h if h.value else None  # (kept on an argument error, released by the library on any other)
-        self.eng._chk(rc)
+        h = _take_over(self.eng, reuse, lambda out: self.eng.lib.bsk_sets_compare_counted(self.eng.ctx, self.h, other.h, limit, out))
         res = reuse if reuse is not None else Compare(self.eng)
         res._bind(h, np.diff(self.offsets()), (self, other))
         return res
@@ -428,22 +431,12 @@ class Sets:
         self.eng._chk(self.eng.lib.bsk_sets_plan(self.h, C.byref(p), n))
         return dict(plan=(p.value or b"").decode(), n_by_path=[int(n[0]), int(n[1]), int(n[2])])
 
-    def close(self):
-        if self.h:
-            self.eng.lib.bsk_sets_release(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Compare:
+class Compare(_Owner):
     """Dense all-pairs comparison (bsk_compare): shared[n_a, n_b] and total[n_a, n_b] (u32), fetched on first use; after
     Sets.compare_counted also dot[n_a, n_b] and min_sum[n_a, n_b] (u64)."""
 
+    _release = "bsk_compare_release"
     _whost = _norms = _operands = None  # the weighted side: (dot, min_sum); (sumsq_a, sumsq_b, totals_a, totals_b); the two Sets
 
     def __init__(self, eng: "Engine"):
@@ -592,20 +585,11 @@ class Compare:
         out[nz] = 1.0 - 2.0 * m[nz] / den[nz]
         return out
 
-    def close(self):
-        if self.h:
-            self.eng.lib.bsk_compare_release(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Index:
+class Index(_Owner):
     """Device-resident inverted index of target sets (bsk_index): value -> ascending target ids."""
+
+    _release = "bsk_index_release"
 
     def __init__(self, eng: "Engine", handle, target_sizes: np.ndarray):
         self.eng, self.h = eng, handle
@@ -621,11 +605,7 @@ class Index:
         """Every (query, target) pair that shares s values with s >= max(min_shared, 1), s >= min_query_cov * |q| and
         s >= min_target_cov * |t| (bsk_index_search).  reuse: the Hits of an earlier search, whose device arrays are kept."""
         sp = L.SearchParams(min_shared, 0, min_query_cov, min_target_cov)
-        h = reuse.h if reuse is not None and reuse.h else C.c_void_p()
-        rc = self.eng.lib.bsk_index_search(self.eng.ctx, self.h, queries.h, C.byref(sp), C.byref(h))
-        if reuse is not None:
-            reuse.h = h if h.value else None  # (kept on an argument error, released by the library on any other)
-        self.eng._chk(rc)
+        h = _take_over(self.eng, reuse, lambda out: self.eng.lib.bsk_index_search(self.eng.ctx, self.h, queries.h, C.byref(sp), out))
         res = reuse if reuse is not None else Hits(self.eng)
         res._bind(h, np.diff(queries.offsets()), self.target_sizes)
         return res
@@ -637,20 +617,11 @@ class Index:
         engine._chk(engine.lib.bsk_index_attach(engine.ctx, self.h, C.byref(h)))
         return Index(engine, h, self.target_sizes)
 
-    def close(self):
-        if self.h:
-            self.eng.lib.bsk_index_release(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Hits:
+class Hits(_Owner):
     """CSR hits of one search (bsk_hits): offsets[n_queries+1], target[] ascending inside a query, shared[]; fetched on first use."""
+
+    _release = "bsk_hits_release"
 
     def __init__(self, eng: "Engine"):
         self.eng, self.h = eng, None
@@ -674,11 +645,7 @@ class Hits:
     def top(self, n: int, reuse: Optional["Hits"] = None) -> "Hits":
         """Every query's min(n, hits) best hits, largest shared count first, ties by ascending target (bsk_hits_top) -> Hits.
         reuse: the Hits of an earlier top() on this engine, whose device arrays are kept."""
-        h = reuse.h if reuse is not None and reuse.h else C.c_void_p()
-        rc = self.eng.lib.bsk_hits_top(self.eng.ctx, self.h, n, C.byref(h))
-        if reuse is not None:
-            reuse.h = h if h.value else None  # (kept on an argument error, released by the library on any other)
-        self.eng._chk(rc)
+        h = _take_over(self.eng, reuse, lambda out: self.eng.lib.bsk_hits_top(self.eng.ctx, self.h, n, out))
         res = reuse if reuse is not None else Hits(self.eng)
         res._bind(h, self.query_sizes, self.target_sizes)
         return res
@@ -735,20 +702,11 @@ class Hits:
         t = self.target_sizes[self.target.astype(np.int64)].astype(np.float64)
         return s / (q + t - s)
 
-    def close(self):
-        if self.h:
-            self.eng.lib.bsk_hits_release(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Engine:
+class Engine(_Owner):
     """One GPU context (bsk_ctx)."""
+
+    _release, _slot = "bsk_ctx_destroy", "ctx"  # (no .h: a constructor that failed leaves no ctx either, which close() allows for)
 
     def __init__(self, device: int = 0):
         self.lib = L.load()
@@ -813,8 +771,7 @@ class Engine:
         lib = L.load()
         st = L.PipelineStats()
         rc = lib.bsk_pipeline_fastx(device, path.encode(), alphabet, C.byref(params), n_streams, chunk_records, 1 if fetch else 0, C.byref(st))
-        if rc != L.OK:
-            raise _SENTINELS.get(rc) or DeviceError(f"bsk_pipeline_fastx: {lib.bsk_err_name(rc).decode()}")
+        _chk_pipeline(lib, "bsk_pipeline_fastx", rc)
         return st.asdict()
 
     @staticmethod
@@ -828,8 +785,7 @@ class Engine:
         st = L.PipelineStats()
         rc = lib.bsk_pipeline_memory_multi(dev, len(devices), data.ctypes.data, offsets.ctypes.data, len(offsets) - 1, alphabet, C.byref(params),
                                            n_streams, chunk_records, repeat, 1 if fetch else 0, C.byref(st))
-        if rc != L.OK:
-            raise _SENTINELS.get(rc) or DeviceError(f"bsk_pipeline_memory_multi: {lib.bsk_err_name(rc).decode()}")
+        _chk_pipeline(lib, "bsk_pipeline_memory_multi", rc)
         return st.asdict()
 
     @staticmethod
@@ -838,8 +794,7 @@ class Engine:
         dev = (C.c_int * len(devices))(*devices)
         st = L.PipelineStats()
         rc = lib.bsk_pipeline_fastx_multi(dev, len(devices), path.encode(), alphabet, C.byref(params), n_streams, chunk_records, 1 if fetch else 0, C.byref(st))
-        if rc != L.OK:
-            raise _SENTINELS.get(rc) or DeviceError(f"bsk_pipeline_fastx_multi: {lib.bsk_err_name(rc).decode()}")
+        _chk_pipeline(lib, "bsk_pipeline_fastx_multi", rc)
         return st.asdict()
 
     @staticmethod
@@ -871,8 +826,7 @@ class Engine:
         arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
         rc = lib.bsk_pipeline_fastx_files(device, arr, len(paths), alphabet, C.byref(params), n_streams, n_readers, chunk_records, 1 if fetch else 0,
                                           C.byref(st))
-        if rc != L.OK:
-            raise _SENTINELS.get(rc) or DeviceError(f"bsk_pipeline_fastx_files: {lib.bsk_err_name(rc).decode()}")
+        _chk_pipeline(lib, "bsk_pipeline_fastx_files", rc)
         return st.asdict()
 
     @staticmethod
@@ -884,8 +838,7 @@ class Engine:
         st = L.PipelineStats()
         rc = lib.bsk_pipeline_memory(device, data.ctypes.data, offsets.ctypes.data, len(offsets) - 1, alphabet, C.byref(params), n_streams,
                                      chunk_records, repeat, 1 if fetch else 0, C.byref(st))
-        if rc != L.OK:
-            raise _SENTINELS.get(rc) or DeviceError(f"bsk_pipeline_memory: {lib.bsk_err_name(rc).decode()}")
+        _chk_pipeline(lib, "bsk_pipeline_memory", rc)
         return st.asdict()
 
     # -- batches
@@ -987,17 +940,6 @@ class Engine:
 
     def sync(self):
         self._chk(self.lib.bsk_ctx_sync(self.ctx))
-
-    def close(self):
-        if getattr(self, "ctx", None):
-            self.lib.bsk_ctx_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 _default_engine: Optional[Engine] = None

@@ -466,8 +466,25 @@ void bsk_comm_destroy(bsk_ctx *ctx);
 typedef struct bsk_sets bsk_sets;
 enum { BSK_SETS_PER_SEQUENCE = 0, BSK_SETS_WHOLE_BATCH = 1 };
 int bsk_result_sets(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets **out);
-/* The same into an existing object (*sets may be NULL the first time): the device arrays are kept and only grow -- a streaming caller
- * allocates nothing in steady state.  On error the object is released and *sets is NULL. */
+/* The result slot.  The entries below that take bsk_sets **out / **sets, bsk_hits **hits / **top or bsk_compare **cmp read the slot as
+ * well as write it: it holds NULL (the entry makes a new object) or the object of an earlier call on the same context, whose device
+ * arrays are kept and only grow.  Every such entry works in two steps.  What it checks BEFORE it takes the object over fails with the
+ * slot as it was: the object is still the caller's, its contents intact.  Then the object is the entry's -- from here any failure
+ * releases it and leaves the slot NULL, and BSK_OK stores it back.  Which error falls on which side:
+ *   bsk_sets_op, _op_counted, _reduce, _filter_counts, _bottom and bsk_index_search: every BSK_ERR_ARG and the 2^32 limits
+ *     (BSK_ERR_UNSUPPORTED) keep the slot; BSK_ERR_NOMEM and BSK_ERR_DEVICE release.
+ *   bsk_hits_top: every BSK_ERR_ARG keeps the slot; its BSK_ERR_UNSUPPORTED (a sort key beyond 63 bits, known after a read-back),
+ *     BSK_ERR_NOMEM and BSK_ERR_DEVICE release.
+ *   bsk_sets_compare, _compare_counted: every BSK_ERR_ARG keeps the slot; both size limits (BSK_ERR_UNSUPPORTED) are checked after the
+ *     object is taken over and release it, as BSK_ERR_NOMEM and BSK_ERR_DEVICE do.
+ *   bsk_result_sets_reuse, _counted: a NULL `sets` and sets of another context (BSK_ERR_ARG) keep the slot.  Every other error releases:
+ *     a NULL r, a bad scope, a bad scale and a result of another context (BSK_ERR_ARG all four), the 2^32 limit, memory, the device.
+ * bsk_result_sets, bsk_sets_from_host and bsk_index_build only write their slot: it is NULL after an error, whatever it held
+ * (bsk_result_sets: after any error but a NULL argument, which leaves it untouched).
+ *
+ * bsk_result_sets into an existing object (*sets may be NULL the first time): the device arrays are kept and only grow -- a streaming
+ * caller allocates nothing in steady state.  Sets of another context are refused and stay in the slot; on every other error the object
+ * is released and *sets is NULL. */
 int bsk_result_sets_reuse(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets **sets);
 /* All sets to the host in narrow form: u32 offsets[n_sets + 1] (narrowed on the device) + the values, copied on the context's stream
  * (4 bytes per set + 8 per value over the link). */
@@ -486,8 +503,8 @@ void bsk_sets_release(bsk_sets *s);
  * set of a is combined with that one set (broadcast: masking a host set out of every read set).  Anything else is BSK_ERR_ARG, as
  * is an unknown op.  The output has a's number of sets, strictly ascending inside a set, and is an ordinary bsk_sets of ctx:
  * index it, search it, fetch it.  a == b (the same object) is legal.  *out: NULL, or the object of an earlier bsk_sets_op /
- * bsk_sets_reduce on this context, whose device arrays are kept and only grow; *out == a or *out == b is BSK_ERR_ARG.  Error rules
- * as bsk_index_search: an argument error leaves *out as it was, any other error releases it and sets *out to NULL.  a and b must
+ * bsk_sets_reduce on this context, whose device arrays are kept and only grow; *out == a or *out == b is BSK_ERR_ARG.  Which error
+ * keeps *out and which releases it: "The result slot" above.  a and b must
  * belong to ctx.  Inputs that hold 2^32 values or more together are BSK_ERR_UNSUPPORTED.  Any u64 is a legal value, 0 and 2^64-1
  * included.  A merge, not a sort: pairs of few values take a group of 16 lanes, larger ones a wavefront, and beyond one
  * wavefront's LDS the merged sequence is cut into tiles that spread over the device (bsk_sets_plan counts the pairs per path). */
@@ -540,8 +557,8 @@ typedef struct bsk_search_params {
  *   s >= max(min_shared, 1)  &&  (double)s >= min_query_cov * (double)|q|  &&  (double)s >= min_target_cov * (double)|t|
  * (IEEE double, exactly this expression).  Hits are CSR by query: offsets[n_queries+1] (u64), target[] (u32) ascending inside a
  * query, shared[] (u32).  *hits may be NULL (new object) or the object of an earlier search on this context: its device arrays are
- * kept and only grow (as bsk_result_sets_reuse); an argument error leaves *hits as it was, any other error releases it and sets
- * *hits to NULL.  queries and ix must belong to ctx.
+ * kept and only grow (as bsk_result_sets_reuse); an argument error and the 2^32 limits leave *hits as it was, a memory or device
+ * error releases it and sets *hits to NULL ("The result slot" above).  queries and ix must belong to ctx.
  * Everything runs on the context's stream; the host reads back sizes only.  A query whose posting lists hold more target ids than
  * one wavefront's LDS budget takes an exact sort-based path instead (bsk_hits_plan counts them). */
 typedef struct bsk_hits bsk_hits;
@@ -568,7 +585,7 @@ int bsk_index_attach(bsk_ctx *ctx, const bsk_index *ix, bsk_index **handle);
 /* For every query of h the min(n, its hit count) hits with the largest shared count (for one query that is the order of
  * containment shared/|q|), ties by ascending target id; inside a query they are stored in that order (NOT ascending by
  * target as bsk_index_search stores them).  *top: NULL or the object of an earlier call on this context (arrays kept,
- * grow only; error rules as bsk_index_search); *top == h is BSK_ERR_ARG.  n == 0 is BSK_ERR_ARG.  The result is an
+ * grow only; errors: "The result slot" above); *top == h is BSK_ERR_ARG.  n == 0 is BSK_ERR_ARG.  The result is an
  * ordinary bsk_hits: _info / _fetch / _device / _release work on it; bsk_hits_plan describes what ran (queries of at most
  * 16 hits: a group of 16 lanes each; more hits and n <= 16: n rounds of a wave-wide maximum; n > 16: a sort in LDS up to
  * 1 024 hits, beyond that one device-wide key sort -- bsk_hits_plan's count is the queries of that last path).
@@ -607,7 +624,7 @@ int bsk_chunk_hits(const bsk_chunk *c, const uint32_t **target, const uint32_t *
  * Every other entry treats such an object as its values only; an entry that writes into a re-used counted object leaves it uncounted
  * (the array is kept, like the others).
  * bsk_result_sets_counted: scope, scale, the 2^32 limit and the *sets rules of bsk_result_sets_reuse (*sets may be NULL; arrays kept,
- * grow only; on error the object is released and *sets is NULL); offsets and values are those of bsk_result_sets, counts[i] is the
+ * grow only; sets of another context stay in the slot, any other error releases the object and *sets is NULL); offsets and values are those of bsk_result_sets, counts[i] is the
  * number of tuples of the set's scope -- the sequence, or the whole batch -- that hold values[i].  Values above MaxUint64 / scale are
  * neither kept nor counted. */
 int bsk_result_sets_counted(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets **sets);
@@ -634,8 +651,8 @@ int bsk_sets_totals(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t co
  * bsk_sets_bottom: out[i] is the min(n, |s[i]|) smallest values of s[i] -- the fixed-size (Mash, sourmash num=) sketch; the sets are
  * ascending, so these are a prefix.  A counted input yields a counted output with the counts of the kept values, an uncounted input an
  * uncounted output.  n == 0 is BSK_ERR_ARG.  *out as in bsk_sets_reduce: NULL, or the object of an earlier op on this context (arrays
- * kept, grow only); *out == s is BSK_ERR_ARG; an argument error leaves *out as it was, any other error releases it and sets *out to
- * NULL.  The result is an ordinary bsk_sets: index it, search it, fetch it, use it in the algebra.
+ * kept, grow only); *out == s is BSK_ERR_ARG; an argument error leaves *out as it was, a memory or device error releases it and sets
+ * *out to NULL.  The result is an ordinary bsk_sets: index it, search it, fetch it, use it in the algebra.
  *
  * bsk_sets_compare: for every pair (i, j), i < n_a, j < n_b, walk the distinct values of a[i] | b[j] in ascending order and stop after
  * `limit` of them (limit == 0: never stop early).  total[i * n_b + j] is the number walked, min(limit, |a[i] | b[j]|);
@@ -646,9 +663,9 @@ int bsk_sets_totals(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t co
  *   bsk_sets_bottom(limit).
  * Any u64 is a legal value, 0 and 2^64-1 included.  a == b (the same object) is legal; the full matrix is computed.  n_a == 0 or
  * n_b == 0 gives an empty result with BSK_OK.  a and b must belong to ctx.  Inputs that together hold 2^32 values or more (a == b:
- * counted once), or more than 2^31 cells, are BSK_ERR_UNSUPPORTED; both are checked before anything is allocated.  *cmp: NULL, or the
- * object of an earlier compare on this context, whose device arrays are kept and only grow; error rules as bsk_index_search (an
- * argument error leaves *cmp as it was, any other error releases it and sets *cmp to NULL).  Everything runs on the context's stream;
+ * counted once), or more than 2^31 cells, are BSK_ERR_UNSUPPORTED; both are checked before any device memory is allocated.  *cmp: NULL, or the
+ * object of an earlier compare on this context, whose device arrays are kept and only grow; an argument error leaves *cmp as it was,
+ * any other error -- the two limits included -- releases it and sets *cmp to NULL ("The result slot" above).  Everything runs on the context's stream;
  * the host reads back one block of figures.
  * Which route for an all-against-all: this one is dense -- its cost is the cells times the values a pair walks, whatever the sets
  * share -- and is the only one that gives the limit-bounded (Mash) numbers; it suits sketches of up to a few thousand values.
