@@ -156,6 +156,27 @@ class Batch(_Owner):
         self.eng._chk(self.eng.lib.bsk_batch_translate(self.eng.ctx, self.h, codon_table, frame, C.byref(h)))
         return Batch(self.eng, h)
 
+    def _refill(self, call):
+        """call(byref(slot)) with this batch's handle in the slot; the object follows the slot (NULL after a refused call)"""
+        h = self.h if self.h else C.c_void_p()
+        self.eng._opts()
+        rc = call(C.byref(h))
+        self.h = h if h.value else None
+        self.eng._chk(rc)
+        return self
+
+    def refill(self, data: np.ndarray, offsets: np.ndarray, alphabet: int = L.ALPHA_DNA) -> "Batch":
+        """bsk_batch_refill_ascii: Engine.batch_from_arrays into THIS object -- its device buffers are kept and only grow, the old contents are gone"""
+        data = np.ascontiguousarray(data, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        return self._refill(lambda slot: self.eng.lib.bsk_batch_refill_ascii(self.eng.ctx, slot, data.ctypes.data, offsets.ctypes.data, len(offsets) - 1, alphabet))
+
+    def refill_packed(self, words: np.ndarray, desc: np.ndarray) -> "Batch":
+        """bsk_batch_refill_packed: Engine.batch_from_packed into THIS object"""
+        words = np.ascontiguousarray(words, np.uint32)
+        desc = np.ascontiguousarray(desc, np.uint64)
+        return self._refill(lambda slot: self.eng.lib.bsk_batch_refill_packed(self.eng.ctx, slot, words.ctypes.data, len(words), desc.ctypes.data, len(desc)))
+
 
 class BatchResult(_Owner):
     """Device-resident CSR result of one bsk_sketch call."""
@@ -199,6 +220,23 @@ class BatchResult(_Owner):
                                                     status.ctypes.data, hash_.ctypes.data,
                                                     pos.ctypes.data if pos is not None else None, max(T, 1)))
         return offs, status[:count], hash_[:T], (pos[:T] if pos is not None else None)
+
+    def fetch_status(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """bsk_result_fetch_status -> status[count]: the BSK_ST_* bytes of reads [first, first + count) alone"""
+        if count is None:
+            count = self.info()["n_reads"] - first
+        status = np.zeros(max(count, 1), np.uint8)
+        self.eng._chk(self.eng.lib.bsk_result_fetch_status(self.eng.ctx, self.h, first, count, status.ctypes.data))
+        return status[:count]
+
+    def device(self):
+        """The result's own arrays ON THE DEVICE, valid until close() or the next run into this object (bsk_result_device, and
+        bsk_result_device_wide for a result over tiles) -> dict(wide, refs, status, hash, pos, first, count): raw pointers, None where the
+        layout has no such array -- refs for a wide result, first / count for the others, pos for the kinds with implicit positions."""
+        refs, status, hash_, pos, first, count = (C.c_void_p() for _ in range(6))
+        self.eng._chk(self.eng.lib.bsk_result_device(self.h, C.byref(refs), C.byref(status), C.byref(hash_), C.byref(pos)))
+        self.eng._chk(self.eng.lib.bsk_result_device_wide(self.h, C.byref(first), C.byref(count)))
+        return dict(wide=not refs.value, refs=refs.value, status=status.value, hash=hash_.value, pos=pos.value, first=first.value, count=count.value)
 
     def fetch_narrow(self, first: int = 0, count: Optional[int] = None):
         """bsk_result_fetch_narrow -> (offsets[count+1] u32, status[count], hash[T], pos[T] u16 (bit 15 = strand) or None)"""

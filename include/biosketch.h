@@ -251,7 +251,10 @@ int bsk_sketch(bsk_ctx *ctx, const bsk_batch *batch, const bsk_params *p, bsk_re
  * per-run duration of the sketch kernel; the call returns after the last run
  * completed.  With *result == NULL one untimed sizing run is done first; with an
  * existing result (from bsk_sketch on the same batch and params) only the
- * warmup + iters launches run.  Used by bench.py (roofline leg). */
+ * warmup + iters launches run.  Used by bench.py (roofline leg).
+ * A result of a class plan (bsk_result_class_plan) repeats the lists its own bsk_sketch left in the context: after a later
+ * bsk_sketch of another such batch or a bsk_batch_prepare on this context the call returns BSK_ERR_ARG and leaves the
+ * result as it was -- call bsk_sketch on it again first. */
 int bsk_sketch_timed(bsk_ctx *ctx, const bsk_batch *batch, const bsk_params *p, bsk_result **result,
                      int warmup, int iters, float *kernel_ms);
 
@@ -297,7 +300,9 @@ int bsk_result_fetch_narrow(bsk_ctx *ctx, const bsk_result *r, uint64_t first, u
  * counterpart: its callers collect Next() values into a slice (e.g. sketches/sketch_test.go:93-104). */
 int bsk_result_compact(bsk_ctx *ctx, const bsk_result *r, const uint64_t **offsets, const uint64_t **hash, const uint32_t **pos,
                        uint64_t *n_tuples);
-/* Device pointers (valid until release / next bsk_sketch on this result); refs[] as described above.
+/* A result owns its arrays: it stays readable through every entry of this section after its batch was re-filled or
+ * destroyed (class plans and tiled calls included: their parts and tile-level results are the library's own).
+ * Device pointers (valid until release / next bsk_sketch on this result); refs[] as described above.
  * Long sequences: when a DNA batch holds a sequence longer than the tile threshold (4096 bases, 512 for the every-position kinds; always from 2^24
  * bases on) the engine cuts the sequences into overlapping tiles, runs the same kernels over the tiles and stitches
  * the tile results back (exactly the tuples of the un-tiled iterator).  Such a result is

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from bio_amd import _lib as L
+from tests.sketch_programs import genetic_codes
 
 pytestmark = pytest.mark.gpu
 
@@ -513,7 +514,9 @@ def test_translate_on_device(engine, oracle, frame):
     reference's own vectors (codon_tables_test.go), every genetic code, IUPAC / gap / junk letters, both encodings."""
     rng = random.Random(40 + frame)
     gold = _codon_golden()
-    for table in (1, 2, 4, 11, 25, 31):
+    tables = genetic_codes(oracle)
+    assert len(tables) == 24 and {1, 2, 4, 11, 25, 31} <= set(tables)  # (seq/codon_tables.go:431-621 registers 24 ids)
+    for table in tables:
         plain = [rand_seq(rng, rng.randint(3, 400)) for _ in range(150)] + [v["nt"].upper() for v in gold["vectors"]]
         mixed = [rand_seq(rng, rng.randint(3, 300), IUPAC) for _ in range(100)]
         mixed += [v["nt"] for v in gold["vectors"]] + ["---ATG---", "AT-GCC* *AA", "ACGTXJ!ACGTAA", "atgNNNtaa", "ATGRAYTGGNNNGCN---TAA"]
@@ -539,7 +542,7 @@ def test_translate_on_device(engine, oracle, frame):
 
 
 @pytest.mark.parametrize("k,w,table,frame", [(9, 5, 1, 1), (9, 5, 11, -1), (10, 3, 4, 2), (3, 1, 1, 3), (5, 4, 2, -3), (12, 4, 1, -2),
-                                             (17, 6, 1, 1)])
+                                             (17, 6, 1, 1), (9, 5, 6, 2), (10, 3, 25, -1)])
 def test_protein_kinds_on_dna_input(engine, oracle, k, w, table, frame):
     """NewProteinIterator / NewProteinMinimizerSketch fed DNA: length checks on the nucleotides (iterator-protein.go:50,
     sketch-protein.go:66,73), then Translate, then the protein path -- a translation with fewer than k residues or fewer
