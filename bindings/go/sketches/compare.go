@@ -130,6 +130,62 @@ func (m *Compare) MashDistance(k int) ([]float64, error) {
 	return j, nil
 }
 
+// ---- sparse all-pairs comparison: the neighbours above a threshold, no matrix --------------------------------------------
+//
+// a.Neighbors(nil, 1000, NeighborParams{JaccardNum: 9, JaccardDen: 10, Upper: true}, nil) walks every pair as Compare does and
+// lists, per set of a, the sets that pass the thresholds: a Hits with Totals, at any number of cells.  h.Top(5, nil) then gives the
+// five nearest neighbours of every set.
+
+// NeighborParams is bsk_neighbor_params: a pair is listed iff shared >= max(MinShared, 1), and, with JaccardDen != 0,
+// shared * JaccardDen >= JaccardNum * total (exact), and, with Upper, j > i.
+type NeighborParams struct {
+	MinShared              uint32
+	JaccardNum, JaccardDen uint32
+	Upper                  bool
+}
+
+// Neighbors compares every set of a with every set of b (nil: of a itself) and keeps the pairs p admits (bsk_sets_neighbors).
+// reuse: nil, or any Hits of this engine, whose device arrays are kept and only grow.
+func (a *Sets) Neighbors(b *Sets, limit uint64, p NeighborParams, reuse *Hits) (*Hits, error) {
+	if b == nil {
+		b = a
+	}
+	if reuse == nil {
+		reuse = &Hits{eng: a.eng}
+		runtime.SetFinalizer(reuse, func(h *Hits) { C.bsk_hits_release(h.h) })
+	}
+	np := C.bsk_neighbor_params{min_shared: C.uint32_t(p.MinShared), jaccard_num: C.uint32_t(p.JaccardNum), jaccard_den: C.uint32_t(p.JaccardDen)}
+	if p.Upper {
+		np.flags = C.BSK_NEIGHBORS_UPPER
+	}
+	rc := C.bsk_sets_neighbors(a.eng.ctx, a.h, b.h, C.uint64_t(limit), &np, &reuse.h)
+	runtime.KeepAlive(a)
+	runtime.KeepAlive(b)
+	return reuse, a.eng.err(rc)
+}
+
+// Totals returns the device address of total[], nil for hits without totals: a search, Top (bsk_hits_totals_device).
+func (h *Hits) Totals() unsafe.Pointer {
+	var t *C.uint32_t
+	C.bsk_hits_totals_device(h.h, &t)
+	runtime.KeepAlive(h)
+	return unsafe.Pointer(t)
+}
+
+// FetchTotals copies the totals of the hits of rows [first, first+count) to the host (bsk_hits_fetch_totals); hits without
+// totals are an error.
+func (h *Hits) FetchTotals(first, count uint64) ([]uint32, error) {
+	offsets, _, _, err := h.Fetch(first, count)
+	if err != nil {
+		return nil, err
+	}
+	n := offsets[count]
+	total := make([]uint32, n+1)
+	rc := C.bsk_hits_fetch_totals(h.eng.ctx, h.h, C.uint64_t(first), C.uint64_t(count), (*C.uint32_t)(unsafe.Pointer(&total[0])), C.uint64_t(n+1))
+	runtime.KeepAlive(h)
+	return total[:n], h.eng.err(rc)
+}
+
 // ---- abundance-weighted comparison of counted sets ------------------------------------------------------------------------
 //
 // a.CompareCounted(b, 0, nil) walks every pair as Compare does and keeps, over the walked values both sets hold, Dot = the sum of

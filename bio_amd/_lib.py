@@ -64,6 +64,11 @@ class Params(C.Structure):
                 ("kind", "k", "w", "s", "m", "scale", "canonical", "circular", "codon_table", "frame")]
 
 
+class NeighborParams(C.Structure):
+    """bsk_neighbor_params (include/biosketch.h)"""
+    _fields_ = [("min_shared", C.c_uint32), ("flags", C.c_uint32), ("jaccard_num", C.c_uint32), ("jaccard_den", C.c_uint32)]
+
+
 class SearchParams(C.Structure):
     """bsk_search_params (include/biosketch.h)"""
     _fields_ = [("min_shared", C.c_uint32), ("reserved", C.c_uint32), ("min_query_cov", C.c_double), ("min_target_cov", C.c_double)]
@@ -188,7 +193,11 @@ SYMBOLS = [
     ("bsk_compare_weights_device", C.c_int, [_vp, _pp, _pp]),
     ("bsk_compare_fetch_weights", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64]),
     ("bsk_sets_sumsq", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp]),
+    ("bsk_sets_neighbors", C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _pp]),
+    ("bsk_hits_totals_device", C.c_int, [_vp, _pp]),
+    ("bsk_hits_fetch_totals", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64]),
 ]
+NEIGHBORS_UPPER = 1
 SETS_PER_SEQUENCE, SETS_WHOLE_BATCH = 0, 1
 SETOP_UNION, SETOP_INTERSECT, SETOP_DIFF, SETOP_SYMDIFF = 0, 1, 2, 3
 MEMBERS_ALL = 0xFFFFFFFF

@@ -272,6 +272,7 @@ void BskOpts::load() {
     tile_min = env_u32("BSK_TILE_MIN", 0);
     tile_pos = env_u32("BSK_TILE_POS", 0);
     test_overflow = env_u32("BSK_TEST_OVERFLOW", 0);
+    nb_room = env_u32("BSK_NB_ROOM", 0);
 }
 extern "C" int bsk_build_has_experiments(void) {
 #ifdef BSK_EXPERIMENTS

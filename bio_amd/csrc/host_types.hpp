@@ -24,6 +24,7 @@ struct BskOpts {
     u32 pf_density = 0;      // BSK_PF_DENSITY (tests): the expected selections per read up to which k_syncmer_pf / _pfl are planned (0: 86 % of what a unit's emit list holds per read -- 1 024 / 1 792 tuples per 64 reads; beyond the list the unit's last reads go to the exact machine)
     bool no_syn_pf = false;  // BSK_NO_SYN_PF: syncmers on k_syncmer_pk / _pkl also where the fused-emit kernel (k_syncmer_pf, round 6) is planned
     bool syn_sel = false;    // BSK_SYN_SEL (make EXPERIMENTS=1): the two-pass syncmer plan, measured and not planned (kernels_syncmer_sel.hpp)
+    u32 nb_room = 0;         // BSK_NB_ROOM (tests): records bsk_sets_neighbors' first run has room for (0: CMP_NB_FIRST_ROOM, compare.hip) -- a case of a few tiles then reaches the second run
     bool no_class = false;   // BSK_NO_CLASS: one plan per batch, keyed on the longest read (rounds 1-4)
     u32 class_min = 16384;   // BSK_CLASS_MIN: batches below this many reads keep one plan
     bool class_view = false;   // BSK_CLASS_VIEW: class plans always cut on the device (k_class_cut + a view of the batch), also where the host's list would do
@@ -33,8 +34,7 @@ struct BskOpts {
 };
 
 // The slots of the context's grow-only pool (bsk_ctx::tmp, taken through ctx_pool below).  A buffer lives from its first use to the end of
-// the context; an entry that shares a slot with another says so here.  A new feature takes the free numbers (38, 39, 47) or adds its own
-// before POOL_SLOTS.
+// the context; an entry that shares a slot with another says so here.  A new feature adds its own numbers before POOL_SLOTS (none is free).
 enum PoolSlot {
     // 0-9 serve two users, each under its own names: a tiled call (tiles.hip) ...
     SLOT_TILE_START = 0, SLOT_TILE_DESC = 1, SLOT_TILE_ADESC = 2, SLOT_TILE_SEQ = 3, SLOT_TILE_SHIFT = 4, SLOT_TILE_KEEP = 5, SLOT_TILE_FLAGS = 6, SLOT_TILE_SEQ_FLAGS = 7,
@@ -63,6 +63,8 @@ enum PoolSlot {
     SLOT_COUNT_RUNS = 40, SLOT_COUNT_KEEP = 41, SLOT_COUNT_POS = 42, SLOT_COUNT_SCAN = 43, SLOT_COUNT_OUT = 44,
     // all-pairs comparison: its figures; bottom-n: its scan (compare.hip)
     SLOT_COMPARE_FIGURES = 45, SLOT_BOTTOM_SCAN = 46,
+    // sparse all-pairs comparison (compare.hip): figures, row counts and scan parts; the kept pairs' records; the sort's keys and storage
+    SLOT_NB_ROWS = 38, SLOT_NB_RECORDS = 39, SLOT_NB_SORT = 47,
     POOL_SLOTS = 48
 };
 

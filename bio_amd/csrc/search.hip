@@ -52,15 +52,6 @@ struct bsk_index {
     IndexArrays *a = nullptr;
 };
 
-struct bsk_hits {
-    bsk_ctx *ctx = nullptr;
-    u64 n_queries = 0, n_hits = 0, n_large = 0;
-    u64 *offsets = nullptr;  // [n_queries + 1]
-    u32 *target = nullptr, *shared = nullptr;
-    size_t c_offsets = 0, c_target = 0, c_shared = 0;  // bytes allocated (grow-only when the object is re-used)
-    char plan[192] = "";
-};
-
 #define SR_CAP 2048  // target ids pass C holds per query: 8 KB of LDS per wavefront
 #define SR_WAVES 4   // wavefronts per workgroup of pass C
 
@@ -732,6 +723,7 @@ extern "C" void bsk_hits_release(bsk_hits *h) {
     (void)hipFree(h->offsets);
     (void)hipFree(h->target);
     (void)hipFree(h->shared);
+    (void)hipFree(h->total);
     delete h;
 }
 
@@ -758,6 +750,7 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
     res->n_queries = nq;
     res->n_hits = 0;
     res->n_large = 0;
+    res->has_total = false;  // (a search into hits with totals keeps the array, like a counted bsk_sets written by an uncounted entry)
     HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (nq + 1) * 8));
     // per-query arrays (one carved buffer) and the query values' posting ranges
     Carve cq;
@@ -862,6 +855,7 @@ static int top_impl(bsk_ctx *ctx, const bsk_hits *h, u32 n, bsk_hits *res) {
     res->n_queries = nq;
     res->n_hits = 0;
     res->n_large = 0;
+    res->has_total = false;  // the n best carry no totals
     HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (nq + 1) * 8));
     // scratch: the search's own slots (its temporaries are dead once its hits exist)
     Carve cq;

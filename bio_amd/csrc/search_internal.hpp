@@ -1,8 +1,25 @@
-// search_internal.hpp -- what search.hip shares with pipeline.cpp (the hits sink).  Nothing here crosses the C ABI.
+// search_internal.hpp -- what search.hip shares with pipeline.cpp (the hits sink) and compare.hip (bsk_sets_neighbors fills a bsk_hits).
+// Nothing here crosses the C ABI.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #include "biosketch.h"
+#include "device_common.hpp"
+
+struct bsk_hits {
+    bsk_ctx *ctx = nullptr;
+    u64 n_queries = 0, n_hits = 0, n_large = 0;
+    u64 *offsets = nullptr;  // [n_queries + 1]
+    u32 *target = nullptr, *shared = nullptr;
+    size_t c_offsets = 0, c_target = 0, c_shared = 0;  // bytes allocated (grow-only when the object is re-used)
+    char plan[192] = "";
+    // hits with totals (compare.hip: bsk_sets_neighbors): total[i] = the values walked for hit i.  `has_total` says whether the array is
+    // valid: every entry that writes hits into this object without totals clears it and keeps the array (grow-only, like the others).
+    u32 *total = nullptr;  // [n_hits]
+    size_t c_total = 0;
+    bool has_total = false;
+};
 
 // All hits of h to the host in the narrow form of a pipeline chunk: u32 offsets[n_queries + 1] (narrowed on the device, as
 // bsk_sets_fetch_narrow narrows a set's), target[] and shared[], copied on the context's stream -- 4 bytes per query + 8 per hit over

@@ -254,6 +254,8 @@ class DeviceSets : public Owned<bsk_sets, bsk_sets_release> {
 
     // ---- MinHash: every set of s cut to its min(n, size) smallest values (counts ride along) INTO this object, as op() ----
     int bottom(Engine &e, const DeviceSets &s, uint64_t n) { return bsk_sets_bottom(e.ctx(), s.get(), n, &p_); }
+    // every set of this object against every set of b, the pairs that pass np only (defined below SearchHits)
+    int neighbors(Engine &e, const DeviceSets &b, uint64_t limit, const bsk_neighbor_params *np, class SearchHits &into) const;
 };
 
 // dense all-pairs comparison (bsk_compare): shared[n_a * n_b] and total[n_a * n_b], row-major
@@ -324,7 +326,29 @@ class SearchHits : public Owned<bsk_hits, bsk_hits_release> {
     // every query's min(n, hits) best hits, largest shared count first, ties by ascending target (bsk_hits_top); into: empty, or the
     // result of an earlier top on this engine (its device arrays are kept and only grow)
     int top(Engine &e, uint32_t n, SearchHits &into) const { return bsk_hits_top(e.ctx(), p_, n, &into.handle()); }
+    // hits with totals (DeviceSets::neighbors): the device array total[n_hits], nullptr for the hits of a search or of top()
+    const uint32_t *totals_device() const {
+        const uint32_t *t = nullptr;
+        bsk_hits_totals_device(p_, &t);
+        return t;
+    }
+    int fetch_totals(Engine &e, std::vector<uint32_t> &total) const {  // BSK_ERR_ARG for hits without totals
+        uint64_t nq = 0, nh = 0;
+        int rc = bsk_hits_info(p_, &nq, &nh);
+        if (rc != BSK_OK) return rc;
+        total.assign(nh + 1, 0);
+        rc = bsk_hits_fetch_totals(e.ctx(), p_, 0, nq, total.data(), nh + 1);
+        total.resize(nh);
+        return rc;
+    }
 };
+
+// sparse all-pairs comparison (bsk_sets_neighbors): per set of a the sets of b that pass np (nullptr: every pair that shares a value),
+// walked as SetsCompare::compare walks them, INTO `into` -- empty, or any hits of this engine (arrays kept, grow only).  The hits carry
+// totals; no matrix is stored and the number of cells is not limited.
+inline int DeviceSets::neighbors(Engine &e, const DeviceSets &b, uint64_t limit, const bsk_neighbor_params *np, SearchHits &into) const {
+    return bsk_sets_neighbors(e.ctx(), p_, b.get(), limit, np, &into.handle());
+}
 
 // inverted index of target sets (bsk_index)
 class SearchIndex : public Owned<bsk_index, bsk_index_release> {

@@ -24,6 +24,7 @@ or CPU implementation here.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Iterable, List, Optional, Sequence, Tuple
 
@@ -462,6 +463,29 @@ class Sets(_Owner):
         res._bind(h, np.diff(self.offsets()), (self, other))
         return res
 
+    def neighbors(self, other: Optional["Sets"] = None, limit: int = 0, min_shared: int = 1, min_jaccard=None, upper: bool = False,
+                  reuse: Optional["Hits"] = None) -> "Hits":
+        """compare() without the matrix (bsk_sets_neighbors): per set of self the sets of other (None: of self) that share at least
+        max(min_shared, 1) of the walked values and, with min_jaccard, have shared / total >= it -- a (num, den) pair of integers,
+        compared exactly, or a float x in 0..1 taken as (ceil(x * 2^30), 2^30).  upper: only pairs with j > i (self against itself:
+        every unordered pair once, the lower triangle never computed).  -> Hits with .total; any number of cells.  reuse: any Hits
+        of this engine, whose device arrays are kept."""
+        other = self if other is None else other
+        num, den = 0, 0
+        if min_jaccard is not None:
+            if isinstance(min_jaccard, tuple):
+                num, den = int(min_jaccard[0]), int(min_jaccard[1])
+            else:
+                x = float(min_jaccard)
+                if not 0.0 <= x <= 1.0:
+                    raise ValueError("min_jaccard outside 0..1")
+                num, den = int(math.ceil(x * (1 << 30))), 1 << 30
+        np_ = L.NeighborParams(min_shared, L.NEIGHBORS_UPPER if upper else 0, num, den)
+        h = _take_over(self.eng, reuse, lambda out: self.eng.lib.bsk_sets_neighbors(self.eng.ctx, self.h, other.h, limit, C.byref(np_), out))
+        res = reuse if reuse is not None else Hits(self.eng)
+        res._bind(h, np.diff(self.offsets()), np.diff(other.offsets()))
+        return res
+
     def plan(self):
         """What made these sets (bsk_sets_plan): a description and the pairs of the last op() that took the group, wave and tiled
         path; sets of any other origin report an empty string and zeros."""
@@ -660,13 +684,14 @@ class Hits(_Owner):
     """CSR hits of one search (bsk_hits): offsets[n_queries+1], target[] ascending inside a query, shared[]; fetched on first use."""
 
     _release = "bsk_hits_release"
+    _totals = None  # total[] of hits with totals (Sets.neighbors), fetched with the others
 
     def __init__(self, eng: "Engine"):
         self.eng, self.h = eng, None
         self._host = None
 
     def _bind(self, h, query_sizes: np.ndarray, target_sizes: np.ndarray):
-        self.h, self._host = h, None
+        self.h, self._host, self._totals = h, None, None
         self.query_sizes, self.target_sizes = query_sizes.astype(np.uint64), target_sizes
 
     def info(self):
@@ -707,9 +732,29 @@ class Hits(_Owner):
         self.eng._chk(self.eng.lib.bsk_hits_fetch(self.eng.ctx, self.h, first, count, offs.ctypes.data, tgt.ctypes.data, sh.ctypes.data, tgt.size))
         return offs, tgt[:n], sh[:n]
 
+    def has_totals(self) -> bool:
+        """whether the last entry that wrote these hits kept totals (bsk_hits_totals_device gives an array): Sets.neighbors does"""
+        if not self.h:
+            return self._totals is not None
+        pt = C.c_void_p()
+        self.eng._chk(self.eng.lib.bsk_hits_totals_device(self.h, C.byref(pt)))
+        return bool(pt.value)
+
+    def fetch_totals(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """bsk_hits_fetch_totals -> total[] of the hits of the range; hits without totals raise"""
+        inf = self.info()
+        if count is None:
+            count = inf["n_queries"] - first
+        tt = np.zeros(max(inf["n_hits"], 1), np.uint32)
+        offs = np.zeros(count + 1, np.uint64)
+        self.eng._chk(self.eng.lib.bsk_hits_fetch(self.eng.ctx, self.h, first, count, offs.ctypes.data, None, None, 0))
+        self.eng._chk(self.eng.lib.bsk_hits_fetch_totals(self.eng.ctx, self.h, first, count, tt.ctypes.data, tt.size))
+        return tt[:int(offs[-1])]
+
     def _cache(self):
         if self._host is None:
             self._host = self.fetch()
+            self._totals = self.fetch_totals() if self.has_totals() else None
         return self._host
 
     @property
@@ -724,6 +769,12 @@ class Hits(_Owner):
     def shared(self) -> np.ndarray:
         return self._cache()[2]
 
+    @property
+    def total(self) -> Optional[np.ndarray]:
+        """per hit the values walked (min(limit, |a | b|)); None for hits without totals (a search, top())"""
+        self._cache()
+        return self._totals
+
     def query(self) -> np.ndarray:
         """the query index of every hit"""
         return np.repeat(np.arange(len(self.offsets) - 1, dtype=np.uint64), np.diff(self.offsets).astype(np.int64))
@@ -734,11 +785,22 @@ class Hits(_Owner):
         return self.shared.astype(np.float64) / q
 
     def jaccard(self) -> np.ndarray:
-        """shared / (|q| + |t| - shared) per hit"""
+        """per hit shared / total where the hits carry totals (Sets.neighbors: the Mash estimator under a limit), else
+        shared / (|q| + |t| - shared)"""
         s = self.shared.astype(np.float64)
+        if self.total is not None:
+            return s / self.total.astype(np.float64)  # (a listed pair shares a value: its total is not 0)
         q = self.query_sizes[self.query().astype(np.int64)].astype(np.float64)
         t = self.target_sizes[self.target.astype(np.int64)].astype(np.float64)
         return s / (q + t - s)
+
+    def mash_distance(self, k: int) -> np.ndarray:
+        """per hit, with j its Jaccard: 1.0 where j is 0, elsewhere max(0, -ln(2j / (1 + j)) / k) -- Compare.mash_distance's formula"""
+        j = self.jaccard()
+        d = np.ones_like(j)
+        nz = j > 0
+        d[nz] = np.maximum(0.0, -np.log(2.0 * j[nz] / (1.0 + j[nz])) / k)
+        return d
 
 
 class Engine(_Owner):

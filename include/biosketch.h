@@ -482,6 +482,8 @@ int bsk_result_sets(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk
  *     BSK_ERR_NOMEM and BSK_ERR_DEVICE release.
  *   bsk_sets_compare, _compare_counted: every BSK_ERR_ARG keeps the slot; both size limits (BSK_ERR_UNSUPPORTED) are checked after the
  *     object is taken over and release it, as BSK_ERR_NOMEM and BSK_ERR_DEVICE do.
+ *   bsk_sets_neighbors: as bsk_sets_compare -- every BSK_ERR_ARG keeps the slot, its size limits (BSK_ERR_UNSUPPORTED), BSK_ERR_NOMEM and
+ *     BSK_ERR_DEVICE release.
  *   bsk_result_sets_reuse, _counted: a NULL `sets` and sets of another context (BSK_ERR_ARG) keep the slot.  Every other error releases:
  *     a NULL r, a bad scope, a bad scale and a result of another context (BSK_ERR_ARG all four), the 2^32 limit, memory, the device.
  * bsk_result_sets, bsk_sets_from_host and bsk_index_build only write their slot: it is NULL after an error, whatever it held
@@ -718,6 +720,50 @@ int bsk_compare_weights_device(const bsk_compare *c, const uint64_t **dot, const
 int bsk_compare_fetch_weights(bsk_ctx *ctx, const bsk_compare *c, uint64_t first_row, uint64_t n_rows,
                               uint64_t *dot, uint64_t *min_sum, uint64_t cell_cap);                       /* either array may be NULL */
 int bsk_sets_sumsq(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t count, uint64_t *sumsq /* host */);
+
+/* ---- sparse all-pairs comparison: the neighbours above a threshold, no matrix ----
+ * bsk_sets_neighbors walks every pair (i, j), i < n_a, j < n_b, exactly as bsk_sets_compare does -- the first `limit` distinct values of
+ * a[i] | b[j], ascending (limit == 0: all of them; any u64 is a legal limit) -- so shared and total of a pair are what bsk_sets_compare
+ * puts in cell (i, j).  No cell is stored.  The pair is listed iff all three hold:
+ *   shared >= max(min_shared, 1)
+ *   jaccard_den == 0  ||  (uint64_t)shared * jaccard_den >= (uint64_t)jaccard_num * total       (exact: no rounding, no division)
+ *   !(flags & BSK_NEIGHBORS_UPPER)  ||  j > i
+ * A pair that shares nothing is never listed, as in the search.  np == NULL is {1, 0, 0, 0}.  A flag bit other than
+ * BSK_NEIGHBORS_UPPER, and jaccard_num > jaccard_den with jaccard_den != 0, are BSK_ERR_ARG.
+ * The result is an ordinary bsk_hits, CSR by the sets of a: offsets[n_a + 1], target[] = j ascending inside a row, shared[], and a fourth
+ * device array total[n_hits] parallel to them (bsk_hits_totals_device, bsk_hits_fetch_totals).  bsk_hits_info / _fetch / _device /
+ * _release and bsk_hits_top work on it unchanged -- bsk_hits_top gives the k nearest neighbours of every set; its OUTPUT carries no
+ * totals (for bottom-n sketches of full size total == limit anyway).  An entry that writes hits without totals into a re-used object
+ * (bsk_index_search, bsk_hits_top, the pipeline's hits sink) leaves it without totals; the array is kept and only grows, like the counts
+ * of a counted bsk_sets.  The result is bit-identical from call to call: nothing in it depends on the order in which workgroups finish.
+ * BSK_NEIGHBORS_UPPER is defined by the indices, so it is legal for a != b too; with a == b (legal with or without the flag) it lists
+ * every unordered pair once, without the diagonal, and the tiles below the diagonal are never run: T (T + 1) / 2 of T x T tiles.
+ * Limits: the operands together hold fewer than 2^32 values (a == b: counted once) and each fewer than 2^32 sets (targets are u32), and
+ * the call keeps fewer than 2^32 pairs, else BSK_ERR_UNSUPPORTED.  There is NO limit on cells: tiles are counted in 64 bits and memory
+ * follows n_a, n_b and the kept pairs, never n_a * n_b.  n_a == 0 or n_b == 0 gives an empty result with BSK_OK.
+ * *hits: NULL, or a bsk_hits of this context, wherever it came from ("The result slot" above): an argument error -- hits of another
+ * context included -- leaves it as it was, any other error releases it and sets *hits to NULL.
+ * Kept pairs are collected in a buffer of records; when a call keeps more than the buffer holds (2^20 the first time, or what a
+ * re-used object already holds) the host reads the exact count and the kernel runs once more.  bsk_hits_plan names the kernel
+ * (k_cmp_tile_nb) and carries tiles=, skipped=, rounds= and runs= as decimal figures; n_large_queries is 0.
+ * bsk_hits_totals_device: *total = NULL for hits without totals.  bsk_hits_fetch_totals: the totals of the hits of rows first ..
+ * first + count - 1, with the range, cap and foreign-context rules of bsk_hits_fetch; BSK_ERR_ARG for hits without totals.
+ * Which route for an all-against-all: bsk_sets_compare when every cell is wanted and there are at most 2^31 of them;
+ * bsk_sets_neighbors when only the pairs above a threshold are (dereplication, clustering, nearest references, the k nearest
+ * neighbours), limit-bounded (Mash) numbers included, at any number of cells -- its cost is still the cells (half of them with
+ * BSK_NEIGHBORS_UPPER) times the values a pair walks; bsk_index_build + bsk_index_search for whole sets (limit == 0 only) of many values
+ * of which most pairs share nothing -- its cost follows the postings. */
+enum { BSK_NEIGHBORS_UPPER = 1 };            /* list only pairs with j > i */
+typedef struct bsk_neighbor_params {
+    uint32_t min_shared;    /* 0 is taken as 1 */
+    uint32_t flags;         /* BSK_NEIGHBORS_UPPER or 0; any other bit: BSK_ERR_ARG */
+    uint32_t jaccard_num;   /* with jaccard_den != 0: keep iff shared * den >= num * total (u64, exact) */
+    uint32_t jaccard_den;   /* 0: no such condition; num > den with den != 0: BSK_ERR_ARG */
+} bsk_neighbor_params;
+int bsk_sets_neighbors(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, uint64_t limit,
+                       const bsk_neighbor_params *np /* NULL: {1,0,0,0} */, bsk_hits **hits);
+int bsk_hits_totals_device(const bsk_hits *h, const uint32_t **total);   /* *total = NULL for hits without totals */
+int bsk_hits_fetch_totals(bsk_ctx *ctx, const bsk_hits *h, uint64_t first, uint64_t count, uint32_t *total, uint64_t hit_cap);
 
 #ifdef __cplusplus
 }
