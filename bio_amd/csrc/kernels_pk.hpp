@@ -24,7 +24,9 @@
 //     element at step j, with key(P_{j-1}) = key(a_0) -- the first of the three checks.
 //   * the block loop (PkMin::run) is two loops: block PAIRS while another block follows the pair and every lane with a read fills both
 //     -- no per-lane window test, both suffix passes unconditional, one scalar compare and branch per pair --, then the ragged variants
-//     for what is left (at least one block; in a fixed-length unit at most two).  The loops carry twice the number of the base that
+//     for what is left (at least one block; in a fixed-length unit at most two).  The block with the longest lane's last window hashes
+//     its live steps only (a scalar compare and branch per step of a ragged block; the steps behind them stage the previous block's
+//     slots and nothing else), and the drain stages that many slots.  The loops carry twice the number of the base that
 //     enters and of the one that leaves at slot 0 as two opaque scalars (bits 5.. index the packed word, bits 0..4 are v_alignbit's
 //     shift): two s_add per block where the compiler re-derived six values from i0.
 // LDS layout: paired columns (lanes l and l + 32 fill one column from both ends) and 16-bit positions as in k_minimizer_fast, 58 rows,
@@ -50,6 +52,17 @@ __device__ __forceinline__ void pk_unroll_impl(std::integer_sequence<int, Is...>
 template <int N, class F>
 __device__ __forceinline__ void pk_unroll(F &&f) {
     pk_unroll_impl(std::make_integer_sequence<int, N>{}, f);
+}
+// f(integral_constant<int, v>) for a wave-uniform v in LO .. HI: a binary tree of scalar compares, one instantiation of f per value
+template <int LO, int HI, class F>
+__device__ __forceinline__ void pk_pick(u32 v, F &&f) {
+    if constexpr (LO == HI) {
+        f(std::integral_constant<int, LO>{});
+    } else {
+        constexpr int MID = (LO + HI) / 2;
+        if (v <= (u32)MID) pk_pick<LO, MID>(v, f);
+        else pk_pick<MID + 1, HI>(v, f);
+    }
 }
 
 // LDS plan of one wavefront.  Paired columns as PLds (kernels_fast.hpp), but 58 rows instead of 56: a column fills up when its two
@@ -209,6 +222,10 @@ struct PkMin {
     // strand << 15 | position (flush_groups and flush_last read it), SELM stages nothing.
     static constexpr bool POS2 = !RINGM && !SELM;
     u32 i2;  // POS2: 2 * i0 of the odd block of the pair being hashed (run() advances it once per pair), in a VGPR
+    // The windows of the wave's longest lane (wave-uniform; run() sets it): a ragged block hashes the steps below it only, and the
+    // drain stages those slots only.  A caller with a block loop of its own (RINGM) sets it after begin(), or leaves it open (~0, begin():
+    // every step is live).
+    u32 nk_top;
 
     __device__ __forceinline__ void set_words(const PkWords &p) {
         wr = (u32x16){p.a.x, p.a.y, p.a.z, p.a.w, p.b.x, p.b.y, p.b.z, p.b.w, p.c.x, p.c.y, p.c.z, p.c.w, p.d.x, p.d.y, p.d.z, p.d.w};
@@ -391,14 +408,31 @@ struct PkMin {
             const u32 nv = (u32)(left < 0 ? 0 : left > W ? W : left);
             vb = (1u << nv) - 1u;
         }
+        // A ragged block may be the wave's last one: its steps from `live` on belong to no window of any lane (they would hash the bases
+        // behind the read -- in a fixed-length batch the next read's -- and feed those k-mers to the tie checks).  Such a step only
+        // stages the previous block's slot; run() stops after this block, so nothing reads the P, S, H or hash state it leaves out.
+        // The test is a scalar compare and branch per step, in the ragged variants alone (if constexpr: the steady blocks and block 0
+        // compile to what they were).
+        constexpr bool CUTB = RAG && !FIRST;
+        u32 live = (u32)W;
+        if constexpr (CUTB) {
+            const u32 left = nk_top - i0;  // (>= 1: run() leaves at i0 >= nk_top)
+            live = (u32)__builtin_amdgcn_readfirstlane((int)(left < (u32)W ? left : (u32)W));
+        }
         pk_unroll<W>([&](auto oc) {
             constexpr int o = decltype(oc)::value;
             if (XC < W && o && o % XC == 0 && o + XC < W) {
                 __builtin_amdgcn_sched_barrier(0);
                 fetch(o + XC);
             }
+            if constexpr (CUTB) {
+                this->template emit<PB + o, o>(pbase);
+                if (o != 0 && (u32)o >= live) return;  // a dead step: the rest of it is skipped
+            }
             roll(xs[o]);
-            if (!FIRST) this->template emit<PB + o, o>(pbase);  // the previous block's slot o, before its registers are re-used
+            if constexpr (!CUTB) {
+                if (!FIRST) this->template emit<PB + o, o>(pbase);  // the previous block's slot o, before its registers are re-used
+            }
             const lmask rev = lt64(rl, rh_, fl, fh_);
             const u32 hl = sel(rev, rl, fl), hh = sel(rev, rh_, fh_);
             if constexpr (POS2) {
@@ -467,9 +501,20 @@ struct PkMin {
         if (!FIRST) asm("v_and_b32_e32 %0, %1, %0" : "+v"(bm) : "n"(PAR ? 0xffff0000u : 0x0000ffffu));
     }
 
-    // the last block's own slots
+    // slots O .. live - 1 of the last block, nested: the first dead slot leaves with one branch
+    template <int PAR, int O>
+    __device__ __forceinline__ void drain_from(u32 pbase, u32 live) {
+        if constexpr (O < W) {
+            if (O == 0 || (u32)O < live) {
+                this->template emit<PAR * 16 + O, O>(pbase);
+                drain_from<PAR, O + 1>(pbase, live);
+            }
+        }
+    }
+
+    // the last block's own slots; live (wave-uniform, 1 .. W): the slots that end a window of some lane -- no other has a selection bit
     template <int PAR>
-    __device__ __forceinline__ void drain(u32 i0) {
+    __device__ __forceinline__ void drain(u32 i0, u32 live = (u32)W) {
         if constexpr (SELM) {  // the last block's own word
             const u32 wsel = (bm >> (PAR * 16)) & ((1u << W) - 1u);
             *reinterpret_cast<LDSQ u32 *>(lds + LY::MASK + (i0 / (u32)W) * 256u + (u32)lane * 4u) = wsel;
@@ -478,10 +523,7 @@ struct PkMin {
         }
         const u32 pbase = (u32)__builtin_amdgcn_readfirstlane((int)i0);
         guard();
-        pk_unroll<W>([&](auto oc) {
-            constexpr int o = decltype(oc)::value;
-            this->template emit<PAR * 16 + o, o>(pbase);
-        });
+        drain_from<PAR, 0>(pbase, live);
     }
 
     // state reset, warm-up over the first k-1 bases, and the words of block 0 (as FastMin::begin)
@@ -490,6 +532,7 @@ struct PkMin {
         fl = fh_ = rl = rh_ = 0;
         bm = 0;
         nsel = 0;
+        nk_top = 0xffffffffu;
         c8000 = 0x8000u;
         asm volatile("" : "+v"(c8000));  // (stays a register: as a known constant the compiler re-materialises it, or goes back to select + shift)
         tmin = 0xffffffffu;
@@ -547,10 +590,12 @@ struct PkMin {
     // Two loops.  The steady loop runs block PAIRS (odd, even) while a further block follows the pair and every lane with a read fills
     // both (i0 + 2 W < nk_min): no per-lane window test, both suffix passes unconditional, ONE scalar compare and branch per pair.
     // What is left -- at least one block, in a fixed-length unit at most two -- runs in the ragged variants (a full block's window
-    // mask is all ones there), a compare per block for "another block follows".  The loops carry t2 / p2 (steps()) as opaque scalars:
+    // mask is all ones there), a compare per block for "another block follows"; the last of them hashes min(W, nk_max - i0) steps
+    // (nk_top, steps()) and drain() stages as many slots.  The loops carry t2 / p2 (steps()) as opaque scalars:
     // left to itself the compiler keeps i0 and 2 i0 and re-derives six values per block from them.
     __device__ __forceinline__ void run(u32 nk_max, bool ok, u32 nk_min, u32 slot0, int step, u32 col8) {
         begin(slot0, step, col8);
+        nk_top = nk_max;
         if constexpr (POS2) i2 = (u32)(-2 * W);  // (block 0 is an even block: its slot constants start at 2 W)
         steps<true, false, 0>(2u * ((u32)k - 1u), 0u, 0u, ok ? 1u : 0u);
         if (nk_max <= (u32)W) {
@@ -590,8 +635,11 @@ struct PkMin {
             if (i0 >= nk_max) break;
             suffix_pass();
         }
-        if (last_par) drain<1>(i0 - W);
-        else drain<0>(i0 - W);
+        // (the last block began at i0 - W < nk_max: it holds nk_max - (i0 - W) windows of the longest lane, or W)
+        const u32 left = nk_max - (i0 - (u32)W);
+        const u32 live = (u32)__builtin_amdgcn_readfirstlane((int)(left < (u32)W ? left : (u32)W));
+        if (last_par) drain<1>(i0 - W, live);
+        else drain<0>(i0 - W, live);
     }
 };
 
@@ -602,7 +650,9 @@ struct PkMin {
 // takes its word with v_readlane: no LDS), and a trip is U = 8 rows, so a unit is three trips of two round trips (table entries, then
 // the staged tuples).
 // POS2: the staged u16 is 2 * position + strand (PkMin::POS2), else strand << 15 | position.
-template <int U, class LY = PkLds, bool POS2 = false>
+// TAILR (k_minimizer_pk): the last trip runs the ceil((T - t0) / 64) rows that hold an output instead of U -- at 22 tuples per read a
+// unit of 150-base reads has 23 rows, seven of them in its last trip.
+template <int U, class LY = PkLds, bool POS2 = false, bool TAILR = false>
 __device__ __forceinline__ void pk_copyout(char *lds, int lane, u32 cnt, u32 excl, u32 T, u64 base, const KArgs &a) {
     constexpr int NH = LY::NHEADS;
     u64 *s_heads = reinterpret_cast<u64 *>(lds + LY::HEADS);
@@ -628,11 +678,13 @@ __device__ __forceinline__ void pk_copyout(char *lds, int lane, u32 cnt, u32 exc
     const char *sh = lds + LY::SH, *sp = lds + LY::SP;
     u64 *const gh = a.hash + base;
     u32 *const gp = a.pos + base;
-    auto trip = [&](u32 t0, auto check) {
+    // R: the rows of the trip (U, or in the last trip the rows that hold an output: the rows before the last one are whole)
+    auto trip = [&](u32 t0, auto rows, auto check) {
+        constexpr int R = decltype(rows)::value;
         constexpr bool CHECK = decltype(check)::value;
-        u32 rank[U];
+        u32 rank[R];
 #pragma unroll
-        for (int j = 0; j < U; ++j) {
+        for (int j = 0; j < R; ++j) {
             const u32 c = (t0 >> 6) + j;  // < 64; words from NH on read as 0: rows beyond the unit see no heads
             const u32 mlo = (u32)__builtin_amdgcn_readlane((int)hw_lo, (int)c), mhi = (u32)__builtin_amdgcn_readlane((int)hw_hi, (int)c);
             // byte offset of the owner's table entry: (bits below this lane << 3) + 8 * (bits of the words before): one v_lshl_add_u32 with
@@ -642,7 +694,9 @@ __device__ __forceinline__ void pk_copyout(char *lds, int lane, u32 cnt, u32 exc
         }
         u64 ent[U];
 #pragma unroll
-        for (int j = 0; j < U; ++j) ent[j] = *reinterpret_cast<const u64 *>(reinterpret_cast<const char *>(s_tab64) + rank[j]);  // (< 64 entries: at most 63 bits are set)
+        for (int j = 0; j < R; ++j) ent[j] = *reinterpret_cast<const u64 *>(reinterpret_cast<const char *>(s_tab64) + rank[j]);  // (< 64 entries: at most 63 bits are set)
+#pragma unroll
+        for (int j = R; j < U; ++j) ent[j] = ent[R - 1];  // (the wait below names U registers: a short trip names its last one again)
         // (one wait for the whole trip: left alone the compiler waits before every first use -- 22 s_waitcnt per trip, each an issue slot)
         if constexpr (U == 8) {
             __builtin_amdgcn_sched_barrier(0);
@@ -652,14 +706,16 @@ __device__ __forceinline__ void pk_copyout(char *lds, int lane, u32 cnt, u32 exc
         u64 hv[U];
         u32 pv[U];
 #pragma unroll
-        for (int j = 0; j < U; ++j) {
+        for (int j = 0; j < R; ++j) {
             const u32 t = t0 + 64 * j + lane;
             const int off = __mul24((int)t, (int)(u32)(ent[j] >> 32)) + (int)(u32)ent[j];  // v_mad_i32_i24
-            const u32 so = (!CHECK || t < T) ? (u32)off : 0u;
+            const u32 so = (!CHECK || (TAILR && j < R - 1) || t < T) ? (u32)off : 0u;
             hv[j] = *reinterpret_cast<const u64 *>(sh + so);
             if constexpr (POS2) pv[j] = *reinterpret_cast<const u16 *>(sp + (so >> 2));
             else pv[j] = (u32)(int)*reinterpret_cast<const short *>(sp + (so >> 2));  // sign-extending read: the strand bit lands in bit 31
         }
+#pragma unroll
+        for (int j = R; j < U; ++j) hv[j] = hv[R - 1], pv[j] = pv[R - 1];
         if constexpr (U == 8) {
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("" ::"v"(hv[0]), "v"(hv[1]), "v"(hv[2]), "v"(hv[3]), "v"(hv[4]), "v"(hv[5]), "v"(hv[6]), "v"(hv[7]), "v"(pv[0]), "v"(pv[1]),
@@ -667,12 +723,12 @@ __device__ __forceinline__ void pk_copyout(char *lds, int lane, u32 cnt, u32 exc
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
-        for (int j = 0; j < U; ++j) {
+        for (int j = 0; j < R; ++j) {
             const u32 t = t0 + 64 * j + lane;
 #ifdef PK_NOSTORE  // dev: the copy-out's LDS chains without its stores
             asm volatile("" ::"v"(hv[j]), "v"(pv[j]));
 #else
-            if (!CHECK || t < T) {
+            if (!CHECK || (TAILR && j < R - 1) || t < T) {
 #ifndef PK_NOHASHST
                 __builtin_nontemporal_store(hv[j], &gh[t]);  // write-once output: non-temporal, the tuples streaming out do not push the sequences' lines out of the L2
 #else
@@ -689,8 +745,15 @@ __device__ __forceinline__ void pk_copyout(char *lds, int lane, u32 cnt, u32 exc
         }
     };
     u32 t0 = 0;
-    for (; t0 + 64 * U <= T; t0 += 64 * U) trip(t0, std::false_type{});
-    if (t0 < T) trip(t0, std::true_type{});
+    for (; t0 + 64 * U <= T; t0 += 64 * U) trip(t0, std::integral_constant<int, U>{}, std::false_type{});
+    if (t0 < T) {
+        if constexpr (TAILR) {  // one scalar switch picks the trip of 1 .. U rows (a row without an output costs as much as one with 64)
+            const u32 nr = (u32)__builtin_amdgcn_readfirstlane((int)((T - t0 + 63u) >> 6));
+            pk_pick<1, U>(nr, [&](auto rc) { trip(t0, rc, std::true_type{}); });
+        } else {
+            trip(t0, std::integral_constant<int, U>{}, std::true_type{});
+        }
+    }
     wave_sync_lds();
 }
 
@@ -861,7 +924,7 @@ __global__ __launch_bounds__(64, 2) void k_minimizer_pk(KArgs a) {  // two waves
 #ifndef PK_CU
 #define PK_CU 8
 #endif
-        if (T) pk_copyout<PK_CU, LY, PkMin<W, LONG>::POS2>(lds, lane, cnt, excl, T, base, a);
+        if (T) pk_copyout<PK_CU, LY, PkMin<W, LONG>::POS2, true>(lds, lane, cnt, excl, T, base, a);
 #endif
         if (r < a.n) {
             if (!((redo >> lane) & 1)) a.refs[ro] = ((base + excl) << 24) | cnt;  // (listed reads: the list pass writes theirs)

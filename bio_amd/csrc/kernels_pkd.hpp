@@ -98,6 +98,7 @@ __global__ __launch_bounds__(64, 2) void k_minimizer_pkd(KArgs a) {
             pm.nk = nk;
             pm.pw = pw_cur;
             pm.begin((u32)lane * 8u, ok ? (int)RB : 0, 0u);  // (a lane without a read stays on row 0 of its own column)
+            pm.nk_top = nk_max;  // the last block hashes its live steps only (PkMin::steps)
             u32 head = 0, left = 0, wprev = 0;
             // what the lane staged since the last flush, whole groups of G to the read's slab; `last`: everything
             auto flush = [&](bool last) {
@@ -146,8 +147,10 @@ __global__ __launch_bounds__(64, 2) void k_minimizer_pkd(KArgs a) {
                 i0 += (u32)W;
                 par ^= 1;
             }
-            if (par) pm.template drain<0>(i0 - (u32)W);  // the last block's own slots
-            else pm.template drain<1>(i0 - (u32)W);
+            const u32 last_nk = nk_max - (i0 - (u32)W);  // the windows of the longest lane in the last block (wave-uniform)
+            const u32 live = (u32)__builtin_amdgcn_readfirstlane((int)(last_nk < (u32)W ? last_nk : (u32)W));
+            if (par) pm.template drain<0>(i0 - (u32)W, live);  // the last block's own slots
+            else pm.template drain<1>(i0 - (u32)W, live);
             flush(true);
             tmin_lane = pm.tmin;
         }
