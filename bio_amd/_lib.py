@@ -69,6 +69,11 @@ class NeighborParams(C.Structure):
     _fields_ = [("min_shared", C.c_uint32), ("flags", C.c_uint32), ("jaccard_num", C.c_uint32), ("jaccard_den", C.c_uint32)]
 
 
+class ClusterParams(C.Structure):
+    """bsk_cluster_params (include/biosketch.h)"""
+    _fields_ = [("method", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class SearchParams(C.Structure):
     """bsk_search_params (include/biosketch.h)"""
     _fields_ = [("min_shared", C.c_uint32), ("reserved", C.c_uint32), ("min_query_cov", C.c_double), ("min_target_cov", C.c_double)]
@@ -196,8 +201,16 @@ SYMBOLS = [
     ("bsk_sets_neighbors", C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _pp]),
     ("bsk_hits_totals_device", C.c_int, [_vp, _pp]),
     ("bsk_hits_fetch_totals", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64]),
+    ("bsk_hits_cluster", C.c_int, [_vp, _vp, _vp, _vp, _pp]),
+    ("bsk_clusters_info", C.c_int, [_vp, _u64p, _u64p, _u64p]),
+    ("bsk_clusters_plan", C.c_int, [_vp, C.POINTER(C.c_char_p), _u64p]),
+    ("bsk_clusters_fetch", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    ("bsk_clusters_device", C.c_int, [_vp, _pp, _pp, _pp, _pp]),
+    ("bsk_clusters_release", None, [_vp]),
+    ("bsk_hits_from_host", C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _pp]),
 ]
 NEIGHBORS_UPPER = 1
+CLUSTER_COMPONENTS, CLUSTER_GREEDY = 0, 1
 SETS_PER_SEQUENCE, SETS_WHOLE_BATCH = 0, 1
 SETOP_UNION, SETOP_INTERSECT, SETOP_DIFF, SETOP_SYMDIFF = 0, 1, 2, 3
 MEMBERS_ALL = 0xFFFFFFFF

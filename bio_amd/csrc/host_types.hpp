@@ -65,7 +65,9 @@ enum PoolSlot {
     SLOT_COMPARE_FIGURES = 45, SLOT_BOTTOM_SCAN = 46,
     // sparse all-pairs comparison (compare.hip): figures, row counts and scan parts; the kept pairs' records; the sort's keys and storage
     SLOT_NB_ROWS = 38, SLOT_NB_RECORDS = 39, SLOT_NB_SORT = 47,
-    POOL_SLOTS = 48
+    // clusters of hits (cluster.hip): figures and per-node arrays; the hits' rows and the edges in rank space; the sorts' keys and storage
+    SLOT_CLUSTER_NODES = 48, SLOT_CLUSTER_EDGES = 49, SLOT_CLUSTER_SORT = 50,
+    POOL_SLOTS = 51
 };
 
 struct bsk_ctx {

@@ -727,6 +727,45 @@ extern "C" void bsk_hits_release(bsk_hits *h) {
     delete h;
 }
 
+// Hits from the host (the counterpart of bsk_sets_from_host): edges computed elsewhere, or a graph a test states directly.  The CSR is
+// checked on the host before the slot is taken over; the caller's buffers are not retained.
+extern "C" int bsk_hits_from_host(bsk_ctx *ctx, const uint64_t *offsets, uint64_t n_queries, const uint32_t *target, const uint32_t *shared, const uint32_t *total,
+                                  bsk_hits **hits) {
+    if (!ctx || !offsets || !hits) return fail_arg(ctx, "bsk_hits_from_host: null argument");
+    if (*hits && (*hits)->ctx != ctx) return fail_arg(ctx, "bsk_hits_from_host: the hits belong to another context");
+    if (offsets[0] != 0) return fail_arg(ctx, "bsk_hits_from_host: offsets[0] != 0");
+    for (u64 q = 0; q < n_queries; ++q)  // (first: then every offset is <= offsets[n_queries], the number of hits)
+        if (offsets[q + 1] < offsets[q]) return fail_arg(ctx, "bsk_hits_from_host: offsets decrease");
+    const u64 H = offsets[n_queries];
+    if (H && (!target || !shared)) return fail_arg(ctx, "bsk_hits_from_host: null target or shared");
+    for (u64 q = 0; q < n_queries; ++q)
+        for (u64 i = offsets[q] + 1; i < offsets[q + 1]; ++i)
+            if (target[i] <= target[i - 1]) return fail_arg(ctx, "bsk_hits_from_host: targets not strictly ascending inside a row");
+    return take_over(ctx, hits, bsk_hits_release, [&](bsk_hits *res, bool) -> int {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        res->n_queries = n_queries;
+        res->n_hits = 0;
+        res->n_large = 0;
+        res->has_total = false;
+        HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (n_queries + 1) * 8));
+        HIPCHK(ctx, grow_array(&res->target, &res->c_target, (H ? H : 1) * 4));
+        HIPCHK(ctx, grow_array(&res->shared, &res->c_shared, (H ? H : 1) * 4));
+        if (total) HIPCHK(ctx, grow_array(&res->total, &res->c_total, (H ? H : 1) * 4));
+        HIPCHK(ctx, hipMemcpyAsync(res->offsets, offsets, (n_queries + 1) * 8, hipMemcpyHostToDevice, st));
+        if (H) {
+            HIPCHK(ctx, hipMemcpyAsync(res->target, target, H * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(ctx, hipMemcpyAsync(res->shared, shared, H * 4, hipMemcpyHostToDevice, st));
+            if (total) HIPCHK(ctx, hipMemcpyAsync(res->total, total, H * 4, hipMemcpyHostToDevice, st));
+        }
+        HIPCHK(ctx, hipStreamSynchronize(st));  // (the caller's buffers are not retained)
+        res->n_hits = H;
+        res->has_total = total != nullptr;
+        snprintf(res->plan, sizeof res->plan, "from host");
+        return BSK_OK;
+    });
+}
+
 static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, const bsk_search_params *sp, bsk_hits *res);
 extern "C" int bsk_index_search(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *queries, const bsk_search_params *sp, bsk_hits **hits) {
     if (!ctx || !ix || !queries || !sp || !hits) return fail_arg(ctx, "bsk_index_search: null argument");

@@ -21,6 +21,18 @@ struct bsk_hits {
     bool has_total = false;
 };
 
+// clusters of a hits graph (cluster.hip: bsk_hits_cluster)
+struct bsk_clusters {
+    bsk_ctx *ctx = nullptr;
+    u64 n = 0, n_clusters = 0, largest = 0, rounds = 0, edges = 0;
+    u32 *label = nullptr;    // [n]
+    u32 *rep = nullptr;      // [n_clusters] ascending
+    u64 *offsets = nullptr;  // [n_clusters + 1]
+    u32 *members = nullptr;  // [n] ascending inside a cluster
+    size_t c_label = 0, c_rep = 0, c_offsets = 0, c_members = 0;  // bytes allocated (grow-only when the object is re-used)
+    char plan[128] = "";
+};
+
 // All hits of h to the host in the narrow form of a pipeline chunk: u32 offsets[n_queries + 1] (narrowed on the device, as
 // bsk_sets_fetch_narrow narrows a set's), target[] and shared[], copied on the context's stream -- 4 bytes per query + 8 per hit over
 // the link.  BSK_ERR_UNSUPPORTED when h holds 2^32 hits or more (the caller takes bsk_hits_fetch).

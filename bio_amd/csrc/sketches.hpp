@@ -303,9 +303,76 @@ class SetsCompare : public Owned<bsk_compare, bsk_compare_release> {
     void device(const uint32_t *&shared, const uint32_t *&total) const { bsk_compare_device(p_, &shared, &total); }
 };
 
+// clusters of a hits graph (bsk_clusters): label[n], rep[n_clusters] ascending, offsets[n_clusters + 1], members[n]
+class Clusters : public Owned<bsk_clusters, bsk_clusters_release> {
+   public:
+    uint64_t n_items() const { return info(0); }
+    uint64_t n_clusters() const { return info(1); }
+    uint64_t largest() const { return info(2); }
+    // the rounds the host drove and the hits off the diagonal (bsk_clusters_plan)
+    uint64_t rounds() const { return figure(0); }
+    uint64_t edges() const { return figure(1); }
+    std::string plan() const {
+        const char *p = "";
+        bsk_clusters_plan(p_, &p, nullptr);
+        return p ? p : "";
+    }
+    int fetch(Engine &e, std::vector<uint32_t> &label, std::vector<uint32_t> &rep, std::vector<uint64_t> &offsets, std::vector<uint32_t> &members) const {
+        uint64_t n = 0, nc = 0;
+        int rc = bsk_clusters_info(p_, &n, &nc, nullptr);
+        if (rc != BSK_OK) return rc;
+        label.assign(n + 1, 0);
+        rep.assign(nc + 1, 0);
+        offsets.assign(nc + 1, 0);
+        members.assign(n + 1, 0);
+        rc = bsk_clusters_fetch(e.ctx(), p_, label.data(), rep.data(), offsets.data(), members.data());
+        label.resize(n);
+        rep.resize(nc);
+        members.resize(n);
+        return rc;
+    }
+    void device(const uint32_t *&label, const uint32_t *&rep, const uint64_t *&offsets, const uint32_t *&members) const {
+        bsk_clusters_device(p_, &label, &rep, &offsets, &members);
+    }
+
+   private:
+    uint64_t info(int i) const {
+        uint64_t v[3] = {0, 0, 0};
+        bsk_clusters_info(p_, &v[0], &v[1], &v[2]);
+        return v[i];
+    }
+    uint64_t figure(int i) const {
+        uint64_t f[2] = {0, 0};
+        bsk_clusters_plan(p_, nullptr, f);
+        return f[i];
+    }
+};
+
 // hits of a search (bsk_hits): CSR by query, target ids ascending inside a query
 class SearchHits : public Owned<bsk_hits, bsk_hits_release> {
    public:
+    // hits made elsewhere (bsk_hits_from_host): offsets[n + 1] from 0, targets strictly ascending inside a row, shared[] and, if not
+    // empty, total[]; INTO this object (its device arrays are kept and only grow)
+    int from_host(Engine &e, const std::vector<uint64_t> &offsets, const std::vector<uint32_t> &target, const std::vector<uint32_t> &shared,
+                  const std::vector<uint32_t> &total = {}) {
+        return hits_from_host(e, offsets, target, shared, total, *this);
+    }
+    // the hits as an undirected graph over their queries, clustered on the device (bsk_hits_cluster): method BSK_CLUSTER_COMPONENTS or
+    // BSK_CLUSTER_GREEDY; score: one u64 per query (higher is better, ties to the smaller index) or empty for index order; into: empty,
+    // or the clusters of an earlier call on this engine
+    int cluster(Engine &e, uint32_t method, const std::vector<uint64_t> &score, Clusters &into) const {
+        uint64_t nq = 0;
+        bsk_hits_info(p_, &nq, nullptr);
+        if (!score.empty() && score.size() != nq) return BSK_ERR_ARG;
+        const bsk_cluster_params cp{method, 0};
+        return bsk_hits_cluster(e.ctx(), p_, &cp, score.empty() ? nullptr : score.data(), &into.handle());
+    }
+    static int hits_from_host(Engine &e, const std::vector<uint64_t> &offsets, const std::vector<uint32_t> &target, const std::vector<uint32_t> &shared,
+                              const std::vector<uint32_t> &total, SearchHits &into) {
+        if (offsets.empty() || offsets.back() != target.size() || shared.size() != target.size() || (!total.empty() && total.size() != target.size())) return BSK_ERR_ARG;
+        return bsk_hits_from_host(e.ctx(), offsets.data(), offsets.size() - 1, target.empty() ? nullptr : target.data(), shared.empty() ? nullptr : shared.data(),
+                                  total.empty() ? nullptr : total.data(), &into.handle());
+    }
     int fetch(Engine &e, std::vector<uint64_t> &offsets, std::vector<uint32_t> &target, std::vector<uint32_t> &shared) const {
         uint64_t nq = 0, nh = 0;
         int rc = bsk_hits_info(p_, &nq, &nh);

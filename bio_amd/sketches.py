@@ -713,6 +713,26 @@ class Hits(_Owner):
         res._bind(h, self.query_sizes, self.target_sizes)
         return res
 
+    def cluster(self, method="components", score=None, reuse: Optional["Clusters"] = None) -> "Clusters":
+        """The hits read as an undirected graph over their queries, clustered on the device (bsk_hits_cluster) -> Clusters.
+        method "components": the connected components, each represented by its member of best rank; "greedy": by ascending rank a
+        node joins the best representative it neighbours, or becomes one (cd-hit, galah).  score: n u64, higher is better, ties to
+        the smaller index; None: index order.  reuse: the Clusters of an earlier call on this engine, whose device arrays are kept."""
+        m = {"components": L.CLUSTER_COMPONENTS, "greedy": L.CLUSTER_GREEDY}.get(method, method)
+        if not isinstance(m, int):
+            raise ValueError("cluster: method is 'components' or 'greedy'")
+        cp = L.ClusterParams(m, 0)
+        sp = None
+        if score is not None:
+            score = np.ascontiguousarray(score, np.uint64)
+            if score.ndim != 1 or len(score) != self.info()["n_queries"]:
+                raise ValueError("cluster: score must hold one u64 per query")
+            sp = score.ctypes.data if len(score) else None
+        h = _take_over(self.eng, reuse, lambda out: self.eng.lib.bsk_hits_cluster(self.eng.ctx, self.h, C.byref(cp), sp, out))
+        res = reuse if reuse is not None else Clusters(self.eng)
+        res._bind(h)
+        return res
+
     def device(self):
         """bsk_hits_device -> (offsets_ptr, target_ptr, shared_ptr)"""
         po, pt, ps = C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -801,6 +821,72 @@ class Hits(_Owner):
         nz = j > 0
         d[nz] = np.maximum(0.0, -np.log(2.0 * j[nz] / (1.0 + j[nz])) / k)
         return d
+
+
+class Clusters(_Owner):
+    """Clusters of a hits graph (bsk_clusters): label[n], rep[n_clusters] ascending, offsets[n_clusters+1] and members[n]
+    ascending inside a cluster; fetched on first use."""
+
+    _release = "bsk_clusters_release"
+
+    def __init__(self, eng: "Engine"):
+        self.eng, self.h = eng, None
+        self._host = None
+
+    def _bind(self, h):
+        self.h, self._host = h, None
+
+    def info(self):
+        n, nc, lg = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self.eng._chk(self.eng.lib.bsk_clusters_info(self.h, C.byref(n), C.byref(nc), C.byref(lg)))
+        return dict(n_items=n.value, n_clusters=nc.value, largest=lg.value)
+
+    def plan(self):
+        """What ran (bsk_clusters_plan): the kernels' names with n=, edges= and rounds=, and the two figures."""
+        p, f = C.c_char_p(), (C.c_uint64 * 2)()
+        self.eng._chk(self.eng.lib.bsk_clusters_plan(self.h, C.byref(p), f))
+        return dict(plan=(p.value or b"").decode(), rounds=int(f[0]), edges=int(f[1]))
+
+    def device(self):
+        """bsk_clusters_device -> (label_ptr, rep_ptr, offsets_ptr, members_ptr)"""
+        pl, pr, po, pm = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.eng._chk(self.eng.lib.bsk_clusters_device(self.h, C.byref(pl), C.byref(pr), C.byref(po), C.byref(pm)))
+        return pl.value, pr.value, po.value, pm.value
+
+    def fetch(self):
+        """bsk_clusters_fetch -> (label[n], rep[n_clusters], offsets[n_clusters+1], members[n])"""
+        inf = self.info()
+        n, nc = inf["n_items"], inf["n_clusters"]
+        label, rep = np.zeros(max(n, 1), np.uint32), np.zeros(max(nc, 1), np.uint32)
+        offsets, members = np.zeros(nc + 1, np.uint64), np.zeros(max(n, 1), np.uint32)
+        self.eng._chk(self.eng.lib.bsk_clusters_fetch(self.eng.ctx, self.h, label.ctypes.data, rep.ctypes.data, offsets.ctypes.data, members.ctypes.data))
+        return label[:n], rep[:nc], offsets, members[:n]
+
+    def _cache(self):
+        if self._host is None:
+            self._host = self.fetch()
+        return self._host
+
+    @property
+    def label(self) -> np.ndarray:
+        return self._cache()[0]
+
+    @property
+    def rep(self) -> np.ndarray:
+        return self._cache()[1]
+
+    @property
+    def offsets(self) -> np.ndarray:
+        return self._cache()[2]
+
+    @property
+    def members(self) -> np.ndarray:
+        return self._cache()[3]
+
+    @property
+    def sizes(self) -> np.ndarray:
+        """the number of members of every cluster"""
+        return np.diff(self.offsets)
 
 
 class Engine(_Owner):
@@ -970,6 +1056,29 @@ class Engine(_Owner):
         self._chk(self.lib.bsk_sets_from_host(self.ctx, offsets.ctypes.data, len(offsets) - 1, values.ctypes.data if len(values) else None,
                                               C.byref(h)))
         return Sets(self, h)
+
+    def hits_from_arrays(self, offsets: np.ndarray, target: np.ndarray, shared: np.ndarray, total: Optional[np.ndarray] = None,
+                         reuse: Optional["Hits"] = None) -> "Hits":
+        """Hits from the host (bsk_hits_from_host): CSR offsets[n_queries+1] (offsets[0] = 0, offsets[-1] = len(target)), targets
+        strictly ascending inside a row, shared[] and, optionally, total[] -- edges computed elsewhere, ready for Hits.cluster.  The
+        Hits know no set sizes: containment() and the size-based jaccard() are not defined for them."""
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        target = np.ascontiguousarray(target, np.uint32)
+        shared = np.ascontiguousarray(shared, np.uint32)
+        if offsets.ndim != 1 or len(offsets) < 1 or int(offsets[-1]) != len(target) or len(shared) != len(target):
+            raise ValueError("hits_from_arrays: offsets must have n_queries + 1 entries and end at len(target) == len(shared)")
+        if total is not None:
+            total = np.ascontiguousarray(total, np.uint32)
+            if len(total) != len(target):
+                raise ValueError("hits_from_arrays: total must be as long as target")
+            if not len(total):
+                total = np.zeros(1, np.uint32)  # (no hits, but hits WITH totals)
+        nh = len(target)
+        h = _take_over(self, reuse, lambda out: self.lib.bsk_hits_from_host(self.ctx, offsets.ctypes.data, len(offsets) - 1, target.ctypes.data if nh else None,
+                                                                           shared.ctypes.data if nh else None, None if total is None else total.ctypes.data, out))
+        res = reuse if reuse is not None else Hits(self)
+        res._bind(h, np.zeros(len(offsets) - 1, np.uint64), np.zeros(0, np.uint64))
+        return res
 
     def sets_from_arrays_counted(self, offsets: np.ndarray, values: np.ndarray, counts: np.ndarray) -> Sets:
         """sets_from_arrays with counts[len(values)] (u32, none of them 0): bsk_sets_from_host_counted"""

@@ -484,6 +484,8 @@ int bsk_result_sets(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk
  *     object is taken over and release it, as BSK_ERR_NOMEM and BSK_ERR_DEVICE do.
  *   bsk_sets_neighbors: as bsk_sets_compare -- every BSK_ERR_ARG keeps the slot, its size limits (BSK_ERR_UNSUPPORTED), BSK_ERR_NOMEM and
  *     BSK_ERR_DEVICE release.
+ *   bsk_hits_cluster (bsk_clusters **out) and bsk_hits_from_host: every BSK_ERR_ARG and the 2^32 limits keep the slot; BSK_ERR_NOMEM and
+ *     BSK_ERR_DEVICE release.
  *   bsk_result_sets_reuse, _counted: a NULL `sets` and sets of another context (BSK_ERR_ARG) keep the slot.  Every other error releases:
  *     a NULL r, a bad scope, a bad scale and a result of another context (BSK_ERR_ARG all four), the 2^32 limit, memory, the device.
  * bsk_result_sets, bsk_sets_from_host and bsk_index_build only write their slot: it is NULL after an error, whatever it held
@@ -720,6 +722,62 @@ int bsk_compare_weights_device(const bsk_compare *c, const uint64_t **dot, const
 int bsk_compare_fetch_weights(bsk_ctx *ctx, const bsk_compare *c, uint64_t first_row, uint64_t n_rows,
                               uint64_t *dot, uint64_t *min_sum, uint64_t cell_cap);                       /* either array may be NULL */
 int bsk_sets_sumsq(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t count, uint64_t *sumsq /* host */);
+
+/* ---- clusters of a neighbour graph: connected components and greedy representatives ----
+ * (bsk_sets_neighbors, which makes such a graph from sets, is declared below this block: it closes the header.)
+ * bsk_hits_cluster turns hits that are already on the device into clusters with one representative each -- n labels and at most n
+ * representatives cross the link, whatever the number of edges.
+ * The graph of h: the nodes are 0 .. n - 1 with n = n_queries; every hit (i, j) with j != i is an UNDIRECTED edge; diagonal hits and
+ * repeated directions are ignored, so the BSK_NEIGHBORS_UPPER result and the full result of one bsk_sets_neighbors(a, a, ...) cluster
+ * identically.  shared[] and total[] are not read.  A hit with target >= n (rectangular hits: a != b) is BSK_ERR_ARG.
+ * Priority: score[n] (host, not retained) or NULL.  A higher score is a higher priority, ties go to the smaller index; NULL is index
+ * order, index 0 best.  rank[v] is v's position in that order, and "best" below means the smallest rank.
+ *   BSK_CLUSTER_COMPONENTS  the clusters are the connected components (single linkage at the threshold the hits were made with); the
+ *                           representative of a component is its member of best rank.
+ *   BSK_CLUSTER_GREEDY      the sequential rule of cd-hit, galah and dRep's second step: visit the nodes by ascending rank; a node that
+ *                           neighbours a node which is already a representative joins the one of best rank among those, any other
+ *                           node becomes a representative.  Clusters are NOT transitive: a member neighbours its representative,
+ *                           members need not neighbour each other.
+ * The result, the same layout for both: n_clusters; rep[n_clusters] (u32) ascending by index -- cluster c is the cluster of rep[c];
+ * label[n] (u32) the cluster number of every node; offsets[n_clusters + 1] (u64) and members[n] (u32), ascending inside a cluster;
+ * the size of the largest cluster.  It is a function of the graph and the scores alone, bit-identical from call to call.
+ * cp == NULL is {BSK_CLUSTER_COMPONENTS, 0}; an unknown method or any flag bit is BSK_ERR_ARG.  n >= 2^32 or n_hits >= 2^32 is
+ * BSK_ERR_UNSUPPORTED.  n == 0 gives an empty result with BSK_OK.
+ * *out follows "The result slot" above: NULL, or a bsk_clusters of this context whose arrays are kept and only grow.  Every
+ * BSK_ERR_ARG -- h or *out of another context and a target >= n included, which one small device pass finds before the object is taken
+ * over -- and the 2^32 limits keep the slot; BSK_ERR_NOMEM and BSK_ERR_DEVICE release it.
+ * How it runs.  Both methods work in rounds that the HOST drives: a round is two small launches over the edges and the nodes, and the
+ * host reads one word back to decide whether to go on.  Inside a launch workgroups meet only in 32-bit atomics (min / or / add) whose
+ * results nothing reads before the launch ends; everything a kernel reads was written by an earlier launch.  No kernel spins, retries
+ * or waits for another workgroup, and the rounds are capped at n + 1, so a defect ends in BSK_ERR_DEVICE, never in a hang -- and the
+ * number of rounds is itself a function of the input.  Components hook every edge's larger root under the smaller and halve the paths
+ * (k_cl_hook + k_cl_jump): a path of 4 096 nodes takes 14 to 18 rounds, not 4 096.  Greedy decides per round every node whose better
+ * neighbours are all decided (k_cl_mis_scan + k_cl_mis_apply): a handful of rounds on graphs in no particular order, but n ROUNDS in
+ * the worst case -- a path whose nodes are ranked from one end to the other -- each of them two launches; eight rounds go out per
+ * read-back.
+ * bsk_clusters_plan: "k_cl_hook+k_cl_jump, n=... edges=... rounds=..." or "k_cl_mis, n=... edges=... rounds=..." with decimal figures,
+ * and figures[0] = the rounds (components: the last, unchanged one included; greedy: the last round that decided a node), figures[1] =
+ * the hits with j != i.  bsk_clusters_fetch copies the arrays asked for (any pointer may be NULL) into label[n], rep[n_clusters],
+ * offsets[n_clusters + 1], members[n]; clusters of another context are BSK_ERR_ARG.  bsk_clusters_device: the device arrays.
+ * bsk_hits_from_host, the counterpart of bsk_sets_from_host: hits made elsewhere (ANI, alignments) as CSR -- offsets[n_queries + 1]
+ * with offsets[0] == 0 and non-decreasing, target[] strictly ascending inside a row (checked on the host: BSK_ERR_ARG), shared[], and
+ * total[] or NULL for hits without totals.  Host pointers are not retained.  *hits follows "The result slot": every BSK_ERR_ARG keeps it,
+ * BSK_ERR_NOMEM and BSK_ERR_DEVICE release it.  bsk_hits_plan reports "from host". */
+enum { BSK_CLUSTER_COMPONENTS = 0, BSK_CLUSTER_GREEDY = 1 };
+typedef struct bsk_cluster_params {
+    uint32_t method;   /* BSK_CLUSTER_COMPONENTS or BSK_CLUSTER_GREEDY; anything else: BSK_ERR_ARG */
+    uint32_t flags;    /* 0; any bit: BSK_ERR_ARG */
+} bsk_cluster_params;
+typedef struct bsk_clusters bsk_clusters;
+int bsk_hits_cluster(bsk_ctx *ctx, const bsk_hits *h, const bsk_cluster_params *cp /* NULL: {0,0} */,
+                     const uint64_t *score /* host, [n_queries], or NULL */, bsk_clusters **out);
+int bsk_clusters_info(const bsk_clusters *c, uint64_t *n_items, uint64_t *n_clusters, uint64_t *largest);
+int bsk_clusters_plan(const bsk_clusters *c, const char **plan, uint64_t figures[2] /* rounds, edges */);
+int bsk_clusters_fetch(bsk_ctx *ctx, const bsk_clusters *c, uint32_t *label, uint32_t *rep, uint64_t *offsets, uint32_t *members); /* any may be NULL */
+int bsk_clusters_device(const bsk_clusters *c, const uint32_t **label, const uint32_t **rep, const uint64_t **offsets, const uint32_t **members);
+void bsk_clusters_release(bsk_clusters *c);
+int bsk_hits_from_host(bsk_ctx *ctx, const uint64_t *offsets, uint64_t n_queries, const uint32_t *target, const uint32_t *shared,
+                       const uint32_t *total /* NULL: hits without totals */, bsk_hits **hits);
 
 /* ---- sparse all-pairs comparison: the neighbours above a threshold, no matrix ----
  * bsk_sets_neighbors walks every pair (i, j), i < n_a, j < n_b, exactly as bsk_sets_compare does -- the first `limit` distinct values of
