@@ -121,9 +121,7 @@ extern "C" const char *bsk_last_error(const bsk_ctx *ctx) { return ctx ? ctx->er
 // batches
 // ------------------------------------------------------------------------------------
 int grid_for(bsk_ctx *ctx, u64 items, int block) {
-    u64 g = (items + block - 1) / block;
-    u64 cap = (u64)ctx->cus * 16;
-    return (int)std::max<u64>(1, std::min(g, cap));
+    return (int)capped_grid(ctx, (items + block - 1) / block, 16);
 }
 
 extern "C" void bsk_batch_destroy(bsk_batch *b) {
@@ -273,6 +271,7 @@ void BskOpts::load() {
     tile_pos = env_u32("BSK_TILE_POS", 0);
     test_overflow = env_u32("BSK_TEST_OVERFLOW", 0);
     nb_room = env_u32("BSK_NB_ROOM", 0);
+    grid_cap = env_u32("BSK_GRID_CAP", 0);
 }
 extern "C" int bsk_build_has_experiments(void) {
 #ifdef BSK_EXPERIMENTS
@@ -285,6 +284,11 @@ extern "C" int bsk_ctx_reload_options(bsk_ctx *ctx) {
     if (!ctx) return BSK_ERR_ARG;
     ctx->opt.load();
     if (ctx->side) ctx->side->opt = ctx->opt;
+    return BSK_OK;
+}
+extern "C" int bsk_ctx_grid_stats(const bsk_ctx *ctx, uint64_t out[2]) {
+    if (!ctx || !out) return BSK_ERR_ARG;
+    for (int i = 0; i < 2; ++i) out[i] = ctx->grid_stats[i] + (ctx->side ? ctx->side->grid_stats[i] : 0);
     return BSK_OK;
 }
 // the side context of a context's class plans (stream + scratch of its own), and the two events that order its stream with the main one

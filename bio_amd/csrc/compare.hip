@@ -559,7 +559,7 @@ int compare_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit, 
     const u64 tiles_x = (n_b + CMP_COLS - 1) / CMP_COLS, ntiles = ((n_a + CMP_ROWS - 1) / CMP_ROWS) * tiles_x;
     // the inputs hold fewer than 2^32 values together, so no total reaches 2^32 - 1 before its union ends
     const u32 lim = limit == 0 || limit > 0xffffffffull ? 0xffffffffu : (u32)limit;
-    const unsigned grid = (unsigned)std::min<u64>(ntiles, (u64)ctx->cus * (weighted ? CMP_W_BLOCKS_PER_CU : CMP_BLOCKS_PER_CU));
+    const unsigned grid = capped_grid(ctx, ntiles, weighted ? CMP_W_BLOCKS_PER_CU : CMP_BLOCKS_PER_CU);
     if (weighted)
         hipLaunchKernelGGL(k_cmp_tile_w, dim3(grid), dim3(CMP_THREADS), 0, st, (const u64 *)a->offsets, (const u64 *)a->values, (const u32 *)(a->counted ? a->counts : nullptr), n_a,
                            (const u64 *)b->offsets, (const u64 *)b->values, (const u32 *)(b->counted ? b->counts : nullptr), n_b, lim, ntiles, tiles_x, res->shared, res->total,
@@ -610,7 +610,7 @@ int neighbors_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit
     u64 *fig = at<u64>(bq, o_fig), *part = at<u64>(bq, o_part);  // fig: tiles run, rounds, most rounds of a tile, kept pairs, tiles skipped, (scan) hits
     u32 *row_count = at<u32>(bq, o_rows);
     const u32 lim = limit == 0 || limit > 0xffffffffull ? 0xffffffffu : (u32)limit;
-    const unsigned grid = (unsigned)std::min<u64>(ntiles, (u64)ctx->cus * CMP_BLOCKS_PER_CU);
+    const unsigned grid = capped_grid(ctx, ntiles, CMP_BLOCKS_PER_CU);
     u64 kept = 0;
     int runs = 0;
     for (;;) {

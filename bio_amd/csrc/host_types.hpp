@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <new>
 #include <string>
@@ -25,6 +26,7 @@ struct BskOpts {
     bool no_syn_pf = false;  // BSK_NO_SYN_PF: syncmers on k_syncmer_pk / _pkl also where the fused-emit kernel (k_syncmer_pf, round 6) is planned
     bool syn_sel = false;    // BSK_SYN_SEL (make EXPERIMENTS=1): the two-pass syncmer plan, measured and not planned (kernels_syncmer_sel.hpp)
     u32 nb_room = 0;         // BSK_NB_ROOM (tests): records bsk_sets_neighbors' first run has room for (0: CMP_NB_FIRST_ROOM, compare.hip) -- a case of a few tiles then reaches the second run
+    u32 grid_cap = 0;        // BSK_GRID_CAP (tests): at most this many workgroups for every grid capped_grid sizes, on top of its own cap per CU (0: that cap alone) -- shapes of a few hundred sets then run every grid-stride loop's later trips
     bool no_class = false;   // BSK_NO_CLASS: one plan per batch, keyed on the longest read (rounds 1-4)
     u32 class_min = 16384;   // BSK_CLASS_MIN: batches below this many reads keep one plan
     bool class_view = false;   // BSK_CLASS_VIEW: class plans always cut on the device (k_class_cut + a view of the batch), also where the host's list would do
@@ -74,6 +76,7 @@ struct bsk_ctx {
     BskOpts opt;
     int device = 0;
     int cus = 0;
+    mutable u64 grid_stats[2] = {};  // capped_grid: the launches it sized, and those whose cap left fewer workgroups than the work asked for (bsk_ctx_grid_stats)
     hipStream_t stream = nullptr;
     std::string err;
     // per-launch synchronisation scratch
@@ -247,6 +250,20 @@ static inline int fail_arg(bsk_ctx *ctx, const char *what) {
         if (e__ != hipSuccess) return fail_hip(ctx, e__, #call); \
     } while (0)
 
+// The one place a capped grid is sized: every launch of the sets side and the small passes around a sketch call (the two grid_for, the
+// tile grids of compare.hip, bsk_hits_top's wave budget) -- the grids of the planned sketch kernels themselves do not come here and keep
+// ctx->cus.  grid_cap_blocks: the most workgroups such a launch gets, `per_cu` per CU and, with BSK_GRID_CAP, no more than that.  capped_grid: `want` workgroups under that
+// cap, at least one; the kernels behind it cover the rest in a grid-stride loop and none of them waits for another workgroup.
+static inline u64 grid_cap_blocks(const bsk_ctx *ctx, u64 per_cu) {
+    const u64 own = (u64)ctx->cus * per_cu;
+    return ctx->opt.grid_cap ? std::min<u64>(ctx->opt.grid_cap, own) : own;
+}
+static inline unsigned capped_grid(const bsk_ctx *ctx, u64 want, u64 per_cu) {
+    const u64 g = std::max<u64>(1, std::min<u64>(want, grid_cap_blocks(ctx, per_cu)));
+    ++ctx->grid_stats[0];
+    if (g < want) ++ctx->grid_stats[1];
+    return (unsigned)g;
+}
 int grid_for(bsk_ctx *ctx, u64 items, int block) __attribute__((visibility("hidden")));  // biosketch.hip: workgroups of `block` items, at most 16 per CU
 bool spare_flush_all() __attribute__((visibility("hidden")));  // biosketch.hip
 // Every device allocation of the library's host code (this header is in all of its translation units): when the device is out of memory, what the contexts keep in reserve (released

@@ -932,7 +932,7 @@ static int top_impl(bsk_ctx *ctx, const bsk_hits *h, u32 n, bsk_hits *res) {
     }
     if (n_wave) {
         // queries a wavefront looks at per step: one while there are fewer queries than wavefronts (a genome query each), 64 at read scale
-        const u64 waves = (u64)ctx->cus * 8 * TOP_WAVES;
+        const u64 waves = grid_cap_blocks(ctx, 8) * TOP_WAVES;
         u32 qb = 1;
         while (qb < 64 && (u64)qb * waves < nq) qb <<= 1;
         const unsigned grid = grid_for(ctx, (nq + qb - 1) / qb, TOP_WAVES, 8);

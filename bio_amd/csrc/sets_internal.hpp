@@ -161,8 +161,7 @@ inline u64 scan_parts(u64 n) { return (n + SCAN_CHUNK - 1) / SCAN_CHUNK + 2; }  
 // ---- host-side helpers of the sets-side translation units ----
 // workgroups of `per_block` items, at most `blocks_per_cu` per CU and at least one
 inline unsigned grid_for(const bsk_ctx *ctx, u64 items, u64 per_block, u64 blocks_per_cu) {
-    const u64 g = (items + per_block - 1) / per_block;
-    return (unsigned)std::max<u64>(1, std::min<u64>(g, (u64)ctx->cus * blocks_per_cu));
+    return capped_grid(ctx, (items + per_block - 1) / per_block, blocks_per_cu);
 }
 // one pooled buffer carved into aligned pieces: add() every array, take Carve::bytes from the pool, then at() every piece
 struct Carve {

@@ -112,6 +112,7 @@ GO_UNBOUND = {
     "bsk_sketch_timed": "HIP-event timing of repeated launches: bench only",
     "bsk_build_has_experiments": "make EXPERIMENTS=1 probe: tests only",
     "bsk_ctx_reload_options": "developer switches (BSK_*): tests only",
+    "bsk_ctx_grid_stats": "launches sized and cut by the grid cap (BSK_GRID_CAP): tests only",
     "bsk_codon_lut": "host copy of the device codon table: tests only (the reference has its own seq.CodonTables)",
     "bsk_batch_fetch_ascii": "reads a batch back: tests only",
     "bsk_pipeline_run": "C callback form of the consumer loop: a Go host loops Pipeline.Next (no callback across cgo)",
