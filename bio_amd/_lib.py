@@ -96,6 +96,7 @@ SYMBOLS = [
     ("bsk_ctx_sync", C.c_int, [_vp]),
     ("bsk_ctx_reload_options", C.c_int, [_vp]),
     ("bsk_ctx_grid_stats", C.c_int, [_vp, _u64p]),
+    ("bsk_ctx_unit_grid_stats", C.c_int, [_vp, _u64p]),
     ("bsk_build_has_experiments", C.c_int, []),
     ("bsk_last_error", C.c_char_p, [_vp]),
     ("bsk_err_name", C.c_char_p, [C.c_int]),

@@ -272,6 +272,7 @@ void BskOpts::load() {
     test_overflow = env_u32("BSK_TEST_OVERFLOW", 0);
     nb_room = env_u32("BSK_NB_ROOM", 0);
     grid_cap = env_u32("BSK_GRID_CAP", 0);
+    unit_grid = env_u32("BSK_UNIT_GRID", 0);
 }
 extern "C" int bsk_build_has_experiments(void) {
 #ifdef BSK_EXPERIMENTS
@@ -289,6 +290,11 @@ extern "C" int bsk_ctx_reload_options(bsk_ctx *ctx) {
 extern "C" int bsk_ctx_grid_stats(const bsk_ctx *ctx, uint64_t out[2]) {
     if (!ctx || !out) return BSK_ERR_ARG;
     for (int i = 0; i < 2; ++i) out[i] = ctx->grid_stats[i] + (ctx->side ? ctx->side->grid_stats[i] : 0);
+    return BSK_OK;
+}
+extern "C" int bsk_ctx_unit_grid_stats(const bsk_ctx *ctx, uint64_t out[2]) {
+    if (!ctx || !out) return BSK_ERR_ARG;
+    for (int i = 0; i < 2; ++i) out[i] = ctx->unit_grid_stats[i] + (ctx->side ? ctx->side->unit_grid_stats[i] : 0);
     return BSK_OK;
 }
 // the side context of a context's class plans (stream + scratch of its own), and the two events that order its stream with the main one

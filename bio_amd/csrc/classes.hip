@@ -300,7 +300,7 @@ int class_build(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, const std
     } else {
         HIPCHK(ctx, hipMemsetAsync(ctx->d_ticket, 0, 16 * sizeof(u32), ctx->stream));  // [8..15] the classes' cursors
         // (the pass is latency-bound per ticket: every wave the CUs hold)
-        hipLaunchKernelGGL(k_class_cut, dim3(std::min<u32>(nblocks, (u32)ctx->cus * 32)), dim3(64), 0, ctx->stream, b->desc, b->n, nblocks, cc, ctx->d_ticket, ctx->d_ticket + 8,
+        hipLaunchKernelGGL(k_class_cut, dim3(unit_grid(ctx, std::min<u32>(nblocks, (u32)ctx->cus * 32))), dim3(64), 0, ctx->stream, b->desc, b->n, nblocks, cc, ctx->d_ticket, ctx->d_ticket + 8,
                            lists, sdesc, view);
     }
     HIPCHK(ctx, hipGetLastError());

@@ -27,6 +27,7 @@ struct BskOpts {
     bool syn_sel = false;    // BSK_SYN_SEL (make EXPERIMENTS=1): the two-pass syncmer plan, measured and not planned (kernels_syncmer_sel.hpp)
     u32 nb_room = 0;         // BSK_NB_ROOM (tests): records bsk_sets_neighbors' first run has room for (0: CMP_NB_FIRST_ROOM, compare.hip) -- a case of a few tiles then reaches the second run
     u32 grid_cap = 0;        // BSK_GRID_CAP (tests): at most this many workgroups for every grid capped_grid sizes, on top of its own cap per CU (0: that cap alone) -- shapes of a few hundred sets then run every grid-stride loop's later trips
+    u32 unit_grid = 0;       // BSK_UNIT_GRID (tests): at most this many workgroups for every grid unit_grid sizes -- the planned sketch kernels' persistent waves and the unit passes beside them (0: their own size) -- a batch of 83 units then gives every wave several tickets
     bool no_class = false;   // BSK_NO_CLASS: one plan per batch, keyed on the longest read (rounds 1-4)
     u32 class_min = 16384;   // BSK_CLASS_MIN: batches below this many reads keep one plan
     bool class_view = false;   // BSK_CLASS_VIEW: class plans always cut on the device (k_class_cut + a view of the batch), also where the host's list would do
@@ -77,6 +78,7 @@ struct bsk_ctx {
     int device = 0;
     int cus = 0;
     mutable u64 grid_stats[2] = {};  // capped_grid: the launches it sized, and those whose cap left fewer workgroups than the work asked for (bsk_ctx_grid_stats)
+    mutable u64 unit_grid_stats[2] = {};  // unit_grid: the grids it sized, and those BSK_UNIT_GRID left fewer workgroups than they asked for (bsk_ctx_unit_grid_stats)
     hipStream_t stream = nullptr;
     std::string err;
     // per-launch synchronisation scratch
@@ -262,6 +264,19 @@ static inline unsigned capped_grid(const bsk_ctx *ctx, u64 want, u64 per_cu) {
     const u64 g = std::max<u64>(1, std::min<u64>(want, grid_cap_blocks(ctx, per_cu)));
     ++ctx->grid_stats[0];
     if (g < want) ++ctx->grid_stats[1];
+    return (unsigned)g;
+}
+// The grids capped_grid leaves alone -- the persistent waves of a planned sketch kernel (pl.grid, pl.side_grid, the tile unit kernels through
+// them) and the unit passes k_tile_count, k_bin_desc, k_class_cut, k_two_strand: `want` workgroups as the caller sized them, or, with
+// BSK_UNIT_GRID=N (tests), at most N.  Never more than `want`; unset, `want` itself.  Counters of its own (bsk_ctx_unit_grid_stats): capped_grid's are
+// held to exact figures.  NOT for a launch whose kernel takes its units from eight ticket heads and looks back over them (k_translate,
+// k_compact_flags, k_tile_stitch, k_minimizer_pft: device_common.hpp, "tickets from eight heads"): head x hands out the units x, x + 8, ...
+// and a wave starts on its own XCD's head, so with fewer waves than XCDs a wave can wait for a unit nobody has taken.  The kernels behind
+// this helper take tickets from ONE word (next_ticket) and walk a ticket's units upward: a unit only waits for units that run or are done.
+static inline unsigned unit_grid(const bsk_ctx *ctx, u64 want) {
+    const u64 g = ctx->opt.unit_grid ? std::max<u64>(1, std::min<u64>(want, ctx->opt.unit_grid)) : want;
+    ++ctx->unit_grid_stats[0];
+    if (g < want) ++ctx->unit_grid_stats[1];
     return (unsigned)g;
 }
 int grid_for(bsk_ctx *ctx, u64 items, int block) __attribute__((visibility("hidden")));  // biosketch.hip: workgroups of `block` items, at most 16 per CU

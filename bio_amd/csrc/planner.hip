@@ -142,11 +142,12 @@ int ensure_binned(bsk_ctx *ctx, const bsk_batch *b, u32 lo, u32 gran, u32 mlo, u
         b->c_bflags = need_f + need_f / 8;
     }
     const u64 nchunks = (b->n + 4095) / 4096;
+    const unsigned bin_grid = unit_grid(ctx, std::min<u64>(nchunks, (u64)ctx->cus * 4));  // (k_bin_desc strides over the chunks by its grid)
     if (fine)
-        hipLaunchKernelGGL(k_bin_desc<128>, dim3((unsigned)std::min<u64>(nchunks, (u64)ctx->cus * 4)), dim3(512), 0, ctx->stream, b->desc, b->rflags, b->n, lo,
+        hipLaunchKernelGGL(k_bin_desc<128>, dim3(bin_grid), dim3(512), 0, ctx->stream, b->desc, b->rflags, b->n, lo,
                            gran, b->bdesc, b->rflags ? b->bflags : nullptr, mlo, mhi, mpretend);
     else
-        hipLaunchKernelGGL(k_bin_desc<64>, dim3((unsigned)std::min<u64>(nchunks, (u64)ctx->cus * 4)), dim3(512), 0, ctx->stream, b->desc, b->rflags, b->n, lo,
+        hipLaunchKernelGGL(k_bin_desc<64>, dim3(bin_grid), dim3(512), 0, ctx->stream, b->desc, b->rflags, b->n, lo,
                            gran, b->bdesc, b->rflags ? b->bflags : nullptr, mlo, mhi, mpretend);
     HIPCHK(ctx, hipGetLastError());
     b->bin_gran = gran;
@@ -212,7 +213,7 @@ int make_plan(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, Plan &pl) {
                     pl.side_which = K_MIN_DENSE_A;
                     pl.side_slab = slab;
                     pl.side_nunits = (u32)units;
-                    pl.side_grid = (int)std::max<u64>(1, std::min<u64>(units, (u64)ctx->cus * (u64)dense_minimizer_ascii_blocks_per_cu(p->w)));  // (a ticket is one unit)
+                    pl.side_grid = (int)unit_grid(ctx, std::max<u64>(1, std::min<u64>(units, (u64)ctx->cus * (u64)dense_minimizer_ascii_blocks_per_cu(p->w))));  // (a ticket is one unit)
                     pl.side_ring_w = 0;
                 }
             }
@@ -224,7 +225,7 @@ int make_plan(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, Plan &pl) {
                 pl.side_which = K_SYN_FAST_A;
                 pl.side_slab = BSK_SYN_CAP;
                 pl.side_nunits = (u32)units;
-                pl.side_grid = (int)std::max<u64>(1, std::min<u64>(units, (u64)ctx->cus * 4));  // (a ticket is one unit)
+                pl.side_grid = (int)unit_grid(ctx, std::max<u64>(1, std::min<u64>(units, (u64)ctx->cus * 4)));  // (a ticket is one unit)
                 pl.side_ring_w = 0;
             }
             if (few_flagged || pl.side_which == K_MIN_DENSE_A || pl.side_which == K_SYN_FAST_A) return BSK_OK;
@@ -511,7 +512,7 @@ int make_plan_enc(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p, Plan &p
         return BSK_ERR_ARG;
     }
     if (ctx->opt.waves_per_cu) per_cu = (int)ctx->opt.waves_per_cu;  // dev: occupancy experiments
-    pl.grid = (int)std::max<u64>(1, std::min<u64>((u64)ctx->cus * per_cu, pl.nunits));
+    pl.grid = (int)unit_grid(ctx, std::max<u64>(1, std::min<u64>((u64)ctx->cus * per_cu, pl.nunits)));
     pl.ring_entries = (size_t)pl.grid * pl.ring_w * 64;
     return BSK_OK;
 }

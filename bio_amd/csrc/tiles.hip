@@ -193,7 +193,7 @@ int sketch_tiled(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p_in, int c
         TCHK(hipMemsetAsync(ctx->d_ticket, 0, 2 * sizeof(u32), ctx->stream));
         TCHK(hipMemsetAsync(ctx->d_lookback, 0, (size_t)nunits * 8, ctx->stream));
         TileArgs ta{seq, geo, nunits, tstart, ctx->d_ticket, ctx->d_lookback};
-        hipLaunchKernelGGL(k_tile_count, dim3(std::min<u32>(nunits, (u32)ctx->cus * 8)), dim3(64), 0, ctx->stream, ta);
+        hipLaunchKernelGGL(k_tile_count, dim3(unit_grid(ctx, std::min<u32>(nunits, (u32)ctx->cus * 8))), dim3(64), 0, ctx->stream, ta);
         TCHK(hipGetLastError());
         if (defer) {
             nt = b->n_bases / geo.tp + n;
@@ -432,7 +432,7 @@ int sketch_tiled(bsk_ctx *ctx, const bsk_batch *b, const bsk_params *p_in, int c
         TCHK(hipGetLastError());
     }
     if (two_strand && nt) {
-        hipLaunchKernelGGL(k_two_strand, dim3((u32)std::min<u64>(nt, (u64)ctx->cus * 32)), dim3(256), 0, ctx->stream, tres->refs, tt.seq, nt,
+        hipLaunchKernelGGL(k_two_strand, dim3(unit_grid(ctx, std::min<u64>(nt, (u64)ctx->cus * 32))), dim3(256), 0, ctx->stream, tres->refs, tt.seq, nt,
                            tres->hash, fin->hash, fin->wfirst, fin->wcount, fin->status, p->k, b->n_nonacgt ? b->ascii : nullptr, b->aoff, b->pairs);
         TCHK(hipGetLastError());
         hipLaunchKernelGGL(k_two_strand_refs, dim3(grid_for(ctx, n, 256)), dim3(256), 0, ctx->stream, n, fin->wfirst, fin->wcount, fin->status,

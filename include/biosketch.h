@@ -146,6 +146,11 @@ int bsk_ctx_reload_options(bsk_ctx *ctx);
  * those got fewer workgroups than their work asked for, so that their grid-stride loops took a later trip (DESIGN.md "Switches",
  * BSK_GRID_CAP).  Counted from bsk_ctx_create on, never reset. */
 int bsk_ctx_grid_stats(const bsk_ctx *ctx, uint64_t out[2]);
+/* The same for the grids that cap leaves alone -- the persistent waves of the planned sketch kernels and the unit passes beside them:
+ * out[0] = the grids sized on this context (its side context included), out[1] = how many of those BSK_UNIT_GRID (DESIGN.md "Switches")
+ * gave fewer workgroups than they asked for, so that every wave took several tickets of units.  Counters of their own: the entry above
+ * does not see them.  Counted from bsk_ctx_create on, never reset. */
+int bsk_ctx_unit_grid_stats(const bsk_ctx *ctx, uint64_t out[2]);
 int bsk_build_has_experiments(void);               /* 1 iff built with `make EXPERIMENTS=1`: the measured-and-rejected kernels behind BSK_SEG / BSK_WPR are in */
 const char *bsk_last_error(const bsk_ctx *ctx);    /* text of the last BSK_ERR_DEVICE/ARG on this ctx */
 const char *bsk_err_name(int err);                 /* "ErrShortSeq", ... (the reference's names) */

@@ -24,10 +24,11 @@ follows).  `mixed` rows put N / IUPAC letters into every third read.  Everything
 FALLBACK ROWS.  `min_dense_fallback<W>` and `pm_fallback<5,9>` hold a homopolymer as long as the longest read: it outgrows its per-read
 slab, the call abandons k_minimizer_dense / k_prot_minimizer_fast and ends on k_minimizer_fast<W> / k_prot_minimizer, and launch.hip names
 that final plan.  The other fallback -- a batch with more than a quarter of low-complexity reads abandons k_minimizer_pk / _ring / _pkd /
-k_syncmer_pk / _pf and ends on k_minimizer_fast<W <= 13> / k_syncmer_fast<W> -- is not in this table.  The list of reads a packed kernel leaves to the exact machine
+k_syncmer_pk / _pf and ends on k_minimizer_fast<W <= 13> / k_syncmer_fast<W> -- is tested in tests/test_gpu_unit_trips.py (the full segment:
+tests/unit_trips.py, EDGES).  The list of reads a packed kernel leaves to the exact machine
 is cut into one segment per workgroup of AT LEAST 1 024 reads (syn_pk_fixcap, planner.hip; list_append, kernels_generic.hpp), and the
 call only falls back when a segment is full: one workgroup must list more than 1 024 reads, which a batch of a few hundred reads -- at
-most 64 per workgroup -- cannot do whatever it holds.  The instantiations such a call ends on are rows of their own here, planned with
+most 64 per workgroup -- cannot do whatever it holds; there BSK_UNIT_GRID=1 gives one workgroup 1 024 and 1 025 exact-tie reads.  The instantiations such a call ends on are rows of their own here, planned with
 BSK_NO_RING + BSK_NO_DENSE + BSK_NO_PK (minimizers) and BSK_NO_PK (syncmers), and their reads hold the low-complexity share above.
 """
 from __future__ import annotations

@@ -113,6 +113,7 @@ GO_UNBOUND = {
     "bsk_build_has_experiments": "make EXPERIMENTS=1 probe: tests only",
     "bsk_ctx_reload_options": "developer switches (BSK_*): tests only",
     "bsk_ctx_grid_stats": "launches sized and cut by the grid cap (BSK_GRID_CAP): tests only",
+    "bsk_ctx_unit_grid_stats": "unit grids sized and cut by BSK_UNIT_GRID: tests only",
     "bsk_codon_lut": "host copy of the device codon table: tests only (the reference has its own seq.CodonTables)",
     "bsk_batch_fetch_ascii": "reads a batch back: tests only",
     "bsk_pipeline_run": "C callback form of the consumer loop: a Go host loops Pipeline.Next (no callback across cgo)",
