@@ -186,6 +186,51 @@ func (h *Hits) FetchTotals(first, count uint64) ([]uint32, error) {
 	return total[:n], h.eng.err(rc)
 }
 
+// NeighborsCounted is Neighbors with the counts (bsk_sets_neighbors_counted): the same pairs, offsets, targets, shared and totals,
+// and per kept pair Dot and MinSum as CompareCounted defines them (Weights, FetchWeights).  The thresholds of p read shared and
+// total only.  Sets without counts count 1.  reuse: nil, or any Hits of this engine.
+func (a *Sets) NeighborsCounted(b *Sets, limit uint64, p NeighborParams, reuse *Hits) (*Hits, error) {
+	if b == nil {
+		b = a
+	}
+	if reuse == nil {
+		reuse = &Hits{eng: a.eng}
+		runtime.SetFinalizer(reuse, func(h *Hits) { C.bsk_hits_release(h.h) })
+	}
+	np := C.bsk_neighbor_params{min_shared: C.uint32_t(p.MinShared), jaccard_num: C.uint32_t(p.JaccardNum), jaccard_den: C.uint32_t(p.JaccardDen)}
+	if p.Upper {
+		np.flags = C.BSK_NEIGHBORS_UPPER
+	}
+	rc := C.bsk_sets_neighbors_counted(a.eng.ctx, a.h, b.h, C.uint64_t(limit), &np, &reuse.h)
+	runtime.KeepAlive(a)
+	runtime.KeepAlive(b)
+	return reuse, a.eng.err(rc)
+}
+
+// Weights returns the device addresses of dot[] and min_sum[], both nil for hits without weights: anything but NeighborsCounted
+// (bsk_hits_weights_device).
+func (h *Hits) Weights() (dot, minSum unsafe.Pointer) {
+	var d, m *C.uint64_t
+	C.bsk_hits_weights_device(h.h, &d, &m)
+	runtime.KeepAlive(h)
+	return unsafe.Pointer(d), unsafe.Pointer(m)
+}
+
+// FetchWeights copies dot and min_sum of the hits of rows [first, first+count) to the host (bsk_hits_fetch_weights); hits without
+// weights are an error.
+func (h *Hits) FetchWeights(first, count uint64) (dot, minSum []uint64, err error) {
+	offsets, _, _, err := h.Fetch(first, count)
+	if err != nil {
+		return nil, nil, err
+	}
+	n := offsets[count]
+	dot, minSum = make([]uint64, n+1), make([]uint64, n+1)
+	rc := C.bsk_hits_fetch_weights(h.eng.ctx, h.h, C.uint64_t(first), C.uint64_t(count), (*C.uint64_t)(unsafe.Pointer(&dot[0])),
+		(*C.uint64_t)(unsafe.Pointer(&minSum[0])), C.uint64_t(n+1))
+	runtime.KeepAlive(h)
+	return dot[:n], minSum[:n], h.eng.err(rc)
+}
+
 // ---- abundance-weighted comparison of counted sets ------------------------------------------------------------------------
 //
 // a.CompareCounted(b, 0, nil) walks every pair as Compare does and keeps, over the walked values both sets hold, Dot = the sum of

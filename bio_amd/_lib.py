@@ -203,6 +203,9 @@ SYMBOLS = [
     ("bsk_sets_neighbors", C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _pp]),
     ("bsk_hits_totals_device", C.c_int, [_vp, _pp]),
     ("bsk_hits_fetch_totals", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64]),
+    ("bsk_sets_neighbors_counted", C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _pp]),
+    ("bsk_hits_weights_device", C.c_int, [_vp, _pp, _pp]),
+    ("bsk_hits_fetch_weights", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64]),
     ("bsk_hits_cluster", C.c_int, [_vp, _vp, _vp, _vp, _pp]),
     ("bsk_clusters_info", C.c_int, [_vp, _u64p, _u64p, _u64p]),
     ("bsk_clusters_plan", C.c_int, [_vp, C.POINTER(C.c_char_p), _u64p]),

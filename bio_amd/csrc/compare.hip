@@ -37,6 +37,11 @@
 // row as the key (column << 32) | record, the library's segmented key sort orders every row by column (the columns of a row are
 // distinct: the record half of a key never decides), and a gather writes target, shared and total.  k_cmp_tile itself is not touched.
 //
+// k_cmp_tile_nb_w (bsk_sets_neighbors_counted): the rounds, count windows and merge loop of k_cmp_tile_w and the epilogue of k_cmp_tile_nb.
+// The rule reads shared and total only, so the kept pairs and their order are those of k_cmp_tile_nb; a keeping lane stores the same
+// 16-byte record and, at the same slot of a second array, 16 bytes of (dot, min_sum).  k_nb_keys and the key sort run as they are; the
+// gather (k_nb_place_w) reads both arrays by the sorted keys.
+//
 // bsk_sets_bottom: the sizes min(n, size) through the library's scan, then a gather by groups of lanes (8 per set while the kept sets
 // average at most CMP_BT_SMALL values, else a wavefront per set).
 #include <hip/hip_runtime.h>
@@ -54,7 +59,7 @@
 #define CMP_WINDOW 128          // values of a set staged per round: 32 windows x 128 x 8 B = 32 KB of LDS, four workgroups a CU
 #define CMP_BLOCKS_PER_CU 4     // the tile grid's cap
 #define CMP_W_BLOCKS_PER_CU 3   // ... and the weighted tile grid's: its count windows add 16 KB of LDS, three workgroups a CU
-#define CMP_NB_FIRST_ROOM 1048576 // bsk_sets_neighbors: records the first run has room for (16 MB), unless a re-used object holds more
+#define CMP_NB_FIRST_ROOM 1048576 // bsk_sets_neighbors: records the first run has room for (16 MB; weighted: 32 MB in two arrays), unless a re-used object holds more
 #define CMP_BT_SMALL 16        // bsk_sets_bottom: kept values per set (average) up to which a set takes 8 lanes
 #define CMP_BT_BLOCKS_PER_CU 16 // ... and its gather's cap
 #define CMP_THREADS (CMP_ROWS * CMP_COLS)
@@ -458,6 +463,167 @@ __global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile_nb(const u64 *aoff, co
     if (t == 0 && skipped) atomicAdd((unsigned long long *)&fig[4], (unsigned long long)skipped);
 }
 
+// the weighted sparse tile (bsk_sets_neighbors_counted): k_cmp_tile_w's rounds and count windows, k_cmp_tile_nb's epilogue.  The rule reads
+// shared and total only -- the weights are a payload -- so the kept pairs, their slots and row_count[] are those of k_cmp_tile_nb; a keeping
+// lane stores its record and, at the same slot of a second array, (dot, min_sum): two 16-byte stores.
+// LDS: k_cmp_tile_w's windows and cursors and the epilogue's words, three workgroups a CU (CMP_W_BLOCKS_PER_CU) within 160 KiB.
+static_assert((CMP_SETS * CMP_WINDOW) * (8 + 4) + CMP_SETS * (8 + 4 + 4) + 4 + (CMP_THREADS / 64) * 4 + 8 <= 160 * 1024 / CMP_W_BLOCKS_PER_CU,
+              "k_cmp_tile_nb_w: 49 692 bytes of LDS a workgroup, 54 613 available");
+__global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile_nb_w(const u64 *aoff, const u64 *av, const u32 *ac, u64 n_a, const u64 *boff, const u64 *bv, const u32 *bc, u64 n_b,
+                                                              u32 lim, u64 ntiles, u64 tiles_x, NbRule rule, u64 room, uint4 *rec, ulonglong2 *wts, u32 *row_count,
+                                                              u64 *fig) {
+    __shared__ u64 s_a[CMP_ROWS * CMP_WINDOW];
+    __shared__ u64 s_b[CMP_COLS * CMP_WINDOW];
+    __shared__ u32 s_ac[CMP_ROWS * CMP_WINDOW];  // the count of s_a[i]
+    __shared__ u32 s_bc[CMP_COLS * CMP_WINDOW];  // the count of s_b[i]
+    __shared__ u64 s_from[CMP_SETS];
+    __shared__ u32 s_n[CMP_SETS];
+    __shared__ u32 s_cnt[CMP_SETS];
+    __shared__ int s_last;
+    __shared__ u32 s_wk[CMP_THREADS / 64];  // kept pairs of every wavefront of the tile
+    __shared__ u64 s_base;                  // the tile's first record
+    const int t = threadIdx.x, r = t / CMP_COLS, c = t % CMP_COLS;
+    u32 skipped = 0;
+    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const u64 i0 = (tile / tiles_x) * CMP_ROWS, j0 = (tile % tiles_x) * CMP_COLS;
+        if (rule.upper && j0 + CMP_COLS <= i0 + 1) {  // every pair of the tile has j <= i
+            ++skipped;
+            continue;
+        }
+        const u64 *vals = t < CMP_ROWS ? av : bv;
+        u64 base = 0;
+        u32 len = 0, start = 0;
+        if (t < CMP_SETS) {
+            const bool isa = t < CMP_ROWS;
+            const u64 g = isa ? i0 + t : j0 + (t - CMP_ROWS);
+            const u64 *off = isa ? aoff : boff;
+            if (g < (isa ? n_a : n_b)) {
+                base = off[g];
+                const u64 sz = off[g + 1] - base;
+                len = sz < (u64)lim ? (u32)sz : lim;
+            }
+        }
+        const bool pair = i0 + r < n_a && j0 + c < n_b;
+        u32 tot = 0, sh = 0, rounds = 0;
+        u64 dt = 0, ms = 0;
+        for (;;) {
+            u64 cand = 0;
+            bool has = false;
+            if (t < CMP_SETS) {
+                const u32 rem = len - start;
+                has = rem > CMP_WINDOW;
+                s_from[t] = base + start;
+                s_n[t] = has ? CMP_WINDOW : rem;
+                if (has) cand = vals[base + start + CMP_WINDOW];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < CMP_ROWS * CMP_WINDOW / CMP_THREADS; ++k) {
+                const int idx = k * CMP_THREADS + t, s = idx / CMP_WINDOW, j = idx % CMP_WINDOW;
+                if ((u32)j < s_n[s]) {
+                    s_a[idx] = av[s_from[s] + j];
+                    s_ac[idx] = ac ? ac[s_from[s] + j] : 1u;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < CMP_WINDOW / CMP_ROWS; ++k) {
+                const int j = k * CMP_ROWS + r;
+                if ((u32)j < s_n[CMP_ROWS + c]) {
+                    s_b[k * CMP_THREADS + t] = bv[s_from[CMP_ROWS + c] + j];
+                    s_bc[k * CMP_THREADS + t] = bc ? bc[s_from[CMP_ROWS + c] + j] : 1u;
+                }
+            }
+            __syncthreads();
+            if (t < 64) {
+                const bool any = __ballot(has) != 0;
+                u64 vhi = has ? cand : ~0ull;
+                for (int d = 32; d; d >>= 1) {
+                    const u64 o = __shfl_xor(vhi, d, 64);
+                    vhi = o < vhi ? o : vhi;
+                }
+                if (t < CMP_SETS) {
+                    u32 cnt = s_n[t];
+                    if (any) {
+                        u32 lo = 0, hi = cnt;
+                        while (lo < hi) {
+                            const u32 mid = (lo + hi) >> 1;
+                            const u64 v = t < CMP_ROWS ? s_a[t * CMP_WINDOW + mid] : s_b[mid * CMP_COLS + (t - CMP_ROWS)];
+                            if (v < vhi) lo = mid + 1;
+                            else hi = mid;
+                        }
+                        cnt = lo;
+                    }
+                    s_cnt[t] = cnt;
+                    start += cnt;
+                }
+                if (t == 0) s_last = any ? 0 : 1;
+            }
+            __syncthreads();
+            ++rounds;
+            if (pair && tot < lim) {
+                const u32 ea = s_cnt[r], eb = s_cnt[CMP_ROWS + c];
+                u32 ia = 0, ib = 0;
+                if (ea && eb) {
+                    u64 x = s_a[r * CMP_WINDOW], y = s_b[c];
+                    for (;;) {
+                        ++tot;
+                        const bool le = x <= y, ge = x >= y;
+                        if (le && ge) {  // both hold it: its counts, from where the two values were read
+                            const u32 ca = s_ac[r * CMP_WINDOW + ia], cb = s_bc[ib * CMP_COLS + c];
+                            const u64 p = (u64)ca * cb;
+                            ++sh;
+                            dt += p;
+                            dt = dt < p ? ~0ull : dt;  // saturating: a wrapped sum is below its last term
+                            ms += ca < cb ? ca : cb;
+                        }
+                        ia += le ? 1u : 0u;
+                        ib += ge ? 1u : 0u;
+                        if (tot >= lim || ia >= ea || ib >= eb) break;
+                        if (le) x = s_a[r * CMP_WINDOW + ia];
+                        if (ge) y = s_b[ib * CMP_COLS + c];
+                    }
+                }
+                const u32 rest = (ea - ia) + (eb - ib), left = lim - tot;
+                tot += rest < left ? rest : left;
+            }
+            const int last = s_last;
+            if (!__syncthreads_or(pair && tot < lim) || last) break;
+        }
+        // the epilogue of k_cmp_tile_nb: the rule per lane (the weights take no part in it), four ballots, one reservation per tile
+        const u64 gi = i0 + r, gj = j0 + c;
+        const bool keep = pair && sh >= rule.min_shared && (rule.den == 0 || (u64)sh * rule.den >= (u64)rule.num * tot) && (!rule.upper || gj > gi);
+        const u64 m = __ballot(keep);
+        const int lane = t & 63, w = t >> 6;
+        if (lane == 0) s_wk[w] = (u32)__builtin_popcountll(m);
+        __syncthreads();
+        u32 before = 0, tile_kept = 0;
+#pragma unroll
+        for (int q = 0; q < CMP_THREADS / 64; ++q) {
+            before += q < w ? s_wk[q] : 0u;
+            tile_kept += s_wk[q];
+        }
+        if (tile_kept) {  // (the same for every thread of the workgroup)
+            if (t == 0) s_base = atomicAdd((unsigned long long *)&fig[3], (unsigned long long)tile_kept);
+            __syncthreads();
+            const u64 slot = s_base + before + (u32)__builtin_popcountll(m & ((1ull << lane) - 1));
+            if (keep && slot < room) {
+                rec[slot] = make_uint4((u32)gi, (u32)gj, sh, tot);
+                wts[slot] = make_ulonglong2(dt, ms);
+            }
+            if (c == 0) {  // the row's first lane: its 16 bits of the ballot
+                const u32 in_row = (u32)__builtin_popcountll((m >> (lane & 48)) & 0xffffull);
+                if (in_row) atomicAdd(&row_count[gi], in_row);
+            }
+        }
+        if (t == 0) {
+            atomicAdd((unsigned long long *)&fig[0], 1ull);
+            atomicAdd((unsigned long long *)&fig[1], (unsigned long long)rounds);
+            atomicMax((unsigned long long *)&fig[2], (unsigned long long)rounds);
+        }
+    }
+    if (t == 0 && skipped) atomicAdd((unsigned long long *)&fig[4], (unsigned long long)skipped);
+}
+
 // the kept pairs' records to their rows: record s of row i takes a place of [off[i], off[i + 1]) -- which one depends on the order of
 // arrival and does not matter -- as the key (column << 32) | s; the columns of a row are distinct, so sorting a row's keys orders its columns
 __global__ __launch_bounds__(256) void k_nb_keys(const uint4 *rec, u64 n, const u64 *off, u32 *row_count, u64 *keys) {
@@ -474,6 +640,19 @@ __global__ __launch_bounds__(256) void k_nb_place(const u64 *keys, u64 n, const 
         tgt[i] = (u32)(k >> 32);
         sh[i] = p.z;
         tot[i] = p.w;
+    }
+}
+// ... and the weights of the weighted records, by the same keys
+__global__ __launch_bounds__(256) void k_nb_place_w(const u64 *keys, u64 n, const uint4 *rec, const ulonglong2 *wts, u32 *tgt, u32 *sh, u32 *tot, u64 *dot, u64 *msum) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const u64 k = keys[i];
+        const uint4 p = rec[(u32)k];
+        const ulonglong2 q = wts[(u32)k];
+        tgt[i] = (u32)(k >> 32);
+        sh[i] = p.z;
+        tot[i] = p.w;
+        dot[i] = q.x;
+        msum[i] = q.y;
     }
 }
 
@@ -579,56 +758,75 @@ int compare_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit, 
 
 // bsk_sets_neighbors: k_cmp_tile_nb (once more when the kept pairs outgrow the room), the row counts to offsets, the records to their
 // rows, every row into ascending column order, the gather.  Memory follows n_a and the kept pairs, never the cells.
-int neighbors_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit, const NbRule &rule, bsk_hits *res, bool reused) {
+// `weighted` (bsk_sets_neighbors_counted): k_cmp_tile_nb_w, a second record array for (dot, min_sum), and a gather that places them too.
+int neighbors_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit, const NbRule &rule, bsk_hits *res, bool reused, bool weighted) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
+    const char *who = weighted ? "bsk_sets_neighbors_counted" : "bsk_sets_neighbors";
     const u64 n_a = a->n_sets, n_b = b->n_sets;
     res->n_queries = n_a;
     res->n_hits = 0;
     res->n_large = 0;
     res->has_total = false;
+    res->has_weights = false;  // (an unweighted call into weighted hits keeps the two arrays)
     HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (n_a + 1) * 8));
     if (n_a == 0 || n_b == 0) {
         HIPCHK(ctx, hipMemsetAsync(res->offsets, 0, (n_a + 1) * 8, st));
         HIPCHK(ctx, grow_array(&res->target, &res->c_target, 4));
         HIPCHK(ctx, grow_array(&res->shared, &res->c_shared, 4));
         HIPCHK(ctx, grow_array(&res->total, &res->c_total, 4));
+        if (weighted) {
+            HIPCHK(ctx, grow_array(&res->dot, &res->c_dot, 8));
+            HIPCHK(ctx, grow_array(&res->msum, &res->c_msum, 8));
+        }
         HIPCHK(ctx, hipStreamSynchronize(st));
         res->has_total = true;
-        snprintf(res->plan, sizeof res->plan, "bsk_sets_neighbors: no pairs, tiles=0 skipped=0 rounds=0 runs=0");
+        res->has_weights = weighted;
+        snprintf(res->plan, sizeof res->plan, "%s: no pairs, tiles=0 skipped=0 rounds=0 runs=0", who);
         return BSK_OK;
     }
     const u64 tiles_y = (n_a + CMP_ROWS - 1) / CMP_ROWS, tiles_x = (n_b + CMP_COLS - 1) / CMP_COLS, ntiles = tiles_y * tiles_x;  // (both below 2^28: no overflow)
     // the first room: the named constant (or the switch), or what a re-used object already holds; never more than the cells
     u64 room = ctx->opt.nb_room ? ctx->opt.nb_room : CMP_NB_FIRST_ROOM;
-    if (reused) room = std::max<u64>(room, std::min(std::min(res->c_target, res->c_shared), res->c_total) / 4);
+    if (reused) {
+        u64 holds = std::min(std::min(res->c_target, res->c_shared), res->c_total) / 4;  // the smallest array, in elements
+        if (weighted) holds = std::min<u64>(holds, std::min(res->c_dot, res->c_msum) / 8);
+        room = std::max(room, holds);
+    }
     room = std::min(room, n_b > room / n_a ? room : n_a * n_b);
     Carve cq;
     const size_t o_fig = cq.add<u64>(8), o_rows = cq.add<u32>(n_a), o_part = cq.add<u64>(scan_parts(n_a));
-    void *bq = nullptr, *brec = nullptr;
+    void *bq = nullptr, *brec = nullptr, *bwts = nullptr;
     HIPCHK(ctx, ctx_pool(ctx, SLOT_NB_ROWS, cq.bytes, &bq));
     u64 *fig = at<u64>(bq, o_fig), *part = at<u64>(bq, o_part);  // fig: tiles run, rounds, most rounds of a tile, kept pairs, tiles skipped, (scan) hits
     u32 *row_count = at<u32>(bq, o_rows);
     const u32 lim = limit == 0 || limit > 0xffffffffull ? 0xffffffffu : (u32)limit;
-    const unsigned grid = capped_grid(ctx, ntiles, CMP_BLOCKS_PER_CU);
+    const unsigned grid = capped_grid(ctx, ntiles, weighted ? CMP_W_BLOCKS_PER_CU : CMP_BLOCKS_PER_CU);
     u64 kept = 0;
     int runs = 0;
     for (;;) {
         HIPCHK(ctx, ctx_pool(ctx, SLOT_NB_RECORDS, room * 16, &brec));
+        if (weighted) HIPCHK(ctx, ctx_pool(ctx, SLOT_NB_WEIGHTS, room * 16, &bwts));
         HIPCHK(ctx, hipMemsetAsync(bq, 0, o_part, st));  // the figures and the row counts
-        hipLaunchKernelGGL(k_cmp_tile_nb, dim3(grid), dim3(CMP_THREADS), 0, st, (const u64 *)a->offsets, (const u64 *)a->values, n_a, (const u64 *)b->offsets,
-                           (const u64 *)b->values, n_b, lim, ntiles, tiles_x, rule, room, static_cast<uint4 *>(brec), row_count, fig);
+        if (weighted)
+            hipLaunchKernelGGL(k_cmp_tile_nb_w, dim3(grid), dim3(CMP_THREADS), 0, st, (const u64 *)a->offsets, (const u64 *)a->values,
+                               (const u32 *)(a->counted ? a->counts : nullptr), n_a, (const u64 *)b->offsets, (const u64 *)b->values,
+                               (const u32 *)(b->counted ? b->counts : nullptr), n_b, lim, ntiles, tiles_x, rule, room, static_cast<uint4 *>(brec),
+                               static_cast<ulonglong2 *>(bwts), row_count, fig);
+        else
+            hipLaunchKernelGGL(k_cmp_tile_nb, dim3(grid), dim3(CMP_THREADS), 0, st, (const u64 *)a->offsets, (const u64 *)a->values, n_a, (const u64 *)b->offsets,
+                               (const u64 *)b->values, n_b, lim, ntiles, tiles_x, rule, room, static_cast<uint4 *>(brec), row_count, fig);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, read_back(ctx, fig, 5));
         ++runs;
         kept = ctx->h_pinned[3];
         if (kept <= room) break;
         if (runs == 2) {  // (the count of a run does not depend on the room)
-            ctx->err = "bsk_sets_neighbors: the kept pairs changed between two runs";
+            ctx->err = std::string(who) + ": the kept pairs changed between two runs";
             return BSK_ERR_DEVICE;
         }
         if (kept >= (1ULL << 32)) {
-            ctx->err = "bsk_sets_neighbors: 2^32 kept pairs or more (raise the thresholds or split the sets)";
+            ctx->err = std::string(who) + ": 2^32 kept pairs or more (raise the thresholds or split the sets)";
             return BSK_ERR_UNSUPPORTED;
         }
         room = kept;
@@ -639,6 +837,10 @@ int neighbors_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit
     HIPCHK(ctx, grow_array(&res->target, &res->c_target, (kept ? kept : 1) * 4));
     HIPCHK(ctx, grow_array(&res->shared, &res->c_shared, (kept ? kept : 1) * 4));
     HIPCHK(ctx, grow_array(&res->total, &res->c_total, (kept ? kept : 1) * 4));
+    if (weighted) {
+        HIPCHK(ctx, grow_array(&res->dot, &res->c_dot, (kept ? kept : 1) * 8));
+        HIPCHK(ctx, grow_array(&res->msum, &res->c_msum, (kept ? kept : 1) * 8));
+    }
     if (kept) {
         size_t tb = 0;
         HIPCHK(ctx, sets_sort_segments_u64(nullptr, tb, nullptr, nullptr, kept, n_a, res->offsets, st));
@@ -650,41 +852,88 @@ int neighbors_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit
         hipLaunchKernelGGL(k_nb_keys, dim3(grid_for(ctx, kept, 256, 16)), dim3(256), 0, st, rec, kept, (const u64 *)res->offsets, row_count, kin);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, sets_sort_segments_u64(at<char>(bs, o_tmp), tb, kin, kout, kept, n_a, res->offsets, st));
-        hipLaunchKernelGGL(k_nb_place, dim3(grid_for(ctx, kept, 256, 16)), dim3(256), 0, st, (const u64 *)kout, kept, rec, res->target, res->shared, res->total);
+        if (weighted)
+            hipLaunchKernelGGL(k_nb_place_w, dim3(grid_for(ctx, kept, 256, 16)), dim3(256), 0, st, (const u64 *)kout, kept, rec, static_cast<const ulonglong2 *>(bwts),
+                               res->target, res->shared, res->total, res->dot, res->msum);
+        else
+            hipLaunchKernelGGL(k_nb_place, dim3(grid_for(ctx, kept, 256, 16)), dim3(256), 0, st, (const u64 *)kout, kept, rec, res->target, res->shared, res->total);
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, hipStreamSynchronize(st));
     res->n_hits = kept;
     res->has_total = true;
-    snprintf(res->plan, sizeof res->plan, "bsk_sets_neighbors: k_cmp_tile_nb, %llu x %llu pairs, limit %llu, tiles=%llu skipped=%llu rounds=%llu runs=%d", (unsigned long long)n_a,
-             (unsigned long long)n_b, (unsigned long long)limit, (unsigned long long)tiles_run, (unsigned long long)skipped, (unsigned long long)rounds, runs);
+    res->has_weights = weighted;
+    snprintf(res->plan, sizeof res->plan, "%s: %s, %llu x %llu pairs, limit %llu, tiles=%llu skipped=%llu rounds=%llu runs=%d", who, weighted ? "k_cmp_tile_nb_w" : "k_cmp_tile_nb",
+             (unsigned long long)n_a, (unsigned long long)n_b, (unsigned long long)limit, (unsigned long long)tiles_run, (unsigned long long)skipped, (unsigned long long)rounds, runs);
     return BSK_OK;
 }
 
 }  // namespace
 
+namespace {
+int neighbors_entry(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, uint64_t limit, const bsk_neighbor_params *np, bsk_hits **hits, bool weighted);
+}  // namespace
+
 extern "C" int bsk_sets_neighbors(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, uint64_t limit, const bsk_neighbor_params *np, bsk_hits **hits) {
-    if (!ctx || !a || !b || !hits) return fail_arg(ctx, "bsk_sets_neighbors: null argument");
+    return neighbors_entry(ctx, a, b, limit, np, hits, false);
+}
+
+// bsk_sets_neighbors with the counts: the same checks in the same order, the same rule, and (dot, min_sum) beside every kept pair
+extern "C" int bsk_sets_neighbors_counted(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, uint64_t limit, const bsk_neighbor_params *np, bsk_hits **hits) {
+    return neighbors_entry(ctx, a, b, limit, np, hits, true);
+}
+
+namespace {
+// the checks and the *hits rules both entries share; `weighted`: bsk_sets_neighbors_counted
+int neighbors_entry(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, uint64_t limit, const bsk_neighbor_params *np, bsk_hits **hits, bool weighted) {
+    if (!ctx || !a || !b || !hits) return fail_arg(ctx, weighted ? "bsk_sets_neighbors_counted: null argument" : "bsk_sets_neighbors: null argument");
     NbRule rule{1, 0, 0, 0};
     if (np) {
-        if (np->flags & ~(uint32_t)BSK_NEIGHBORS_UPPER) return fail_arg(ctx, "bsk_sets_neighbors: unknown flag");
-        if (np->jaccard_den != 0 && np->jaccard_num > np->jaccard_den) return fail_arg(ctx, "bsk_sets_neighbors: jaccard_num > jaccard_den");
+        if (np->flags & ~(uint32_t)BSK_NEIGHBORS_UPPER) return fail_arg(ctx, weighted ? "bsk_sets_neighbors_counted: unknown flag" : "bsk_sets_neighbors: unknown flag");
+        if (np->jaccard_den != 0 && np->jaccard_num > np->jaccard_den)
+            return fail_arg(ctx, weighted ? "bsk_sets_neighbors_counted: jaccard_num > jaccard_den" : "bsk_sets_neighbors: jaccard_num > jaccard_den");
         rule = NbRule{np->min_shared ? np->min_shared : 1u, np->jaccard_num, np->jaccard_den, np->flags & BSK_NEIGHBORS_UPPER};
     }
-    if (a->ctx != ctx || b->ctx != ctx || (*hits && (*hits)->ctx != ctx)) return fail_arg(ctx, "bsk_sets_neighbors: the sets or the hits belong to another context");
+    if (a->ctx != ctx || b->ctx != ctx || (*hits && (*hits)->ctx != ctx))
+        return fail_arg(ctx, weighted ? "bsk_sets_neighbors_counted: the sets or the hits belong to another context" : "bsk_sets_neighbors: the sets or the hits belong to another context");
     return take_over(ctx, hits, bsk_hits_release, [&](bsk_hits *res, bool reused) -> int {
         // the limits after the slot is taken, as in bsk_sets_compare: a re-used object is released (a == b holds its values once)
         const u64 held = a == b ? a->n_values : a->n_values + b->n_values;
         if (a->n_values >= (1ULL << 32) || b->n_values >= (1ULL << 32) || held >= (1ULL << 32)) {
-            ctx->err = "bsk_sets_neighbors: 2^32 values or more (split the sets)";
+            ctx->err = weighted ? "bsk_sets_neighbors_counted: 2^32 values or more (split the sets)" : "bsk_sets_neighbors: 2^32 values or more (split the sets)";
             return BSK_ERR_UNSUPPORTED;
         }
         if (a->n_sets >= (1ULL << 32) || b->n_sets >= (1ULL << 32)) {  // targets are u32, and so are a record's row and the sort's segments
-            ctx->err = "bsk_sets_neighbors: 2^32 sets or more (split the sets)";
+            ctx->err = weighted ? "bsk_sets_neighbors_counted: 2^32 sets or more (split the sets)" : "bsk_sets_neighbors: 2^32 sets or more (split the sets)";
             return BSK_ERR_UNSUPPORTED;
         }
-        return neighbors_impl(ctx, a, b, limit, rule, res, reused);
+        return neighbors_impl(ctx, a, b, limit, rule, res, reused, weighted);
     });
+}
+}  // namespace
+
+extern "C" int bsk_hits_weights_device(const bsk_hits *h, const uint64_t **dot, const uint64_t **min_sum) {
+    if (!h) return BSK_ERR_ARG;
+    if (dot) *dot = h->has_weights ? (const uint64_t *)h->dot : nullptr;
+    if (min_sum) *min_sum = h->has_weights ? (const uint64_t *)h->msum : nullptr;
+    return BSK_OK;
+}
+
+extern "C" int bsk_hits_fetch_weights(bsk_ctx *ctx, const bsk_hits *h, uint64_t first, uint64_t count, uint64_t *dot, uint64_t *min_sum, uint64_t hit_cap) {
+    if (!ctx || !h) return fail_arg(ctx, "bsk_hits_fetch_weights: null argument");
+    if (h->ctx != ctx) return fail_arg(ctx, "bsk_hits_fetch_weights: the hits belong to another context");
+    if (!h->has_weights) return fail_arg(ctx, "bsk_hits_fetch_weights: the hits carry no weights (bsk_sets_neighbors_counted makes such)");
+    if (first > h->n_queries || count > h->n_queries - first) return fail_arg(ctx, "bsk_hits_fetch_weights: range outside the hits");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned, h->offsets + first, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pinned + 1, h->offsets + first + count, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const u64 o0 = ctx->h_pinned[0], nh = ctx->h_pinned[1] - o0;
+    if (nh > hit_cap) return fail_arg(ctx, "bsk_hits_fetch_weights: hit_cap too small");
+    if (nh && dot) HIPCHK(ctx, hipMemcpyAsync(dot, h->dot + o0, nh * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (nh && min_sum) HIPCHK(ctx, hipMemcpyAsync(min_sum, h->msum + o0, nh * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return BSK_OK;
 }
 
 extern "C" int bsk_hits_totals_device(const bsk_hits *h, const uint32_t **total) {

@@ -70,7 +70,9 @@ enum PoolSlot {
     SLOT_NB_ROWS = 38, SLOT_NB_RECORDS = 39, SLOT_NB_SORT = 47,
     // clusters of hits (cluster.hip): figures and per-node arrays; the hits' rows and the edges in rank space; the sorts' keys and storage
     SLOT_CLUSTER_NODES = 48, SLOT_CLUSTER_EDGES = 49, SLOT_CLUSTER_SORT = 50,
-    POOL_SLOTS = 51
+    // weighted sparse all-pairs comparison (compare.hip): the kept pairs' (dot, min_sum), slot for slot beside SLOT_NB_RECORDS
+    SLOT_NB_WEIGHTS = 51,
+    POOL_SLOTS = 52
 };
 
 struct bsk_ctx {

@@ -19,6 +19,11 @@ struct bsk_hits {
     u32 *total = nullptr;  // [n_hits]
     size_t c_total = 0;
     bool has_total = false;
+    // hits with weights (compare.hip: bsk_sets_neighbors_counted): dot[i] and msum[i] of hit i, as the cells of bsk_sets_compare_counted.
+    // `has_weights` follows the rule of `has_total`: whoever clears that clears this, and the arrays stay.
+    u64 *dot = nullptr, *msum = nullptr;  // [n_hits]
+    size_t c_dot = 0, c_msum = 0;
+    bool has_weights = false;
 };
 
 // clusters of a hits graph (cluster.hip: bsk_hits_cluster)

@@ -20,6 +20,7 @@
 #include <stdexcept>
 #include <string>
 #include <string_view>
+#include <utility>
 #include <vector>
 
 #include "biosketch.h"
@@ -256,6 +257,8 @@ class DeviceSets : public Owned<bsk_sets, bsk_sets_release> {
     int bottom(Engine &e, const DeviceSets &s, uint64_t n) { return bsk_sets_bottom(e.ctx(), s.get(), n, &p_); }
     // every set of this object against every set of b, the pairs that pass np only (defined below SearchHits)
     int neighbors(Engine &e, const DeviceSets &b, uint64_t limit, const bsk_neighbor_params *np, class SearchHits &into) const;
+    // ... and with the counts: the same pairs, and dot and min_sum of every kept pair (defined below SearchHits)
+    int neighbors_counted(Engine &e, const DeviceSets &b, uint64_t limit, const bsk_neighbor_params *np, class SearchHits &into) const;
 };
 
 // dense all-pairs comparison (bsk_compare): shared[n_a * n_b] and total[n_a * n_b], row-major
@@ -408,6 +411,23 @@ class SearchHits : public Owned<bsk_hits, bsk_hits_release> {
         total.resize(nh);
         return rc;
     }
+    // hits with weights (DeviceSets::neighbors_counted): the device arrays dot[n_hits] and min_sum[n_hits], both nullptr for any other hits
+    std::pair<const uint64_t *, const uint64_t *> weights_device() const {
+        const uint64_t *d = nullptr, *m = nullptr;
+        bsk_hits_weights_device(p_, &d, &m);
+        return {d, m};
+    }
+    int fetch_weights(Engine &e, std::vector<uint64_t> &dot, std::vector<uint64_t> &min_sum) const {  // BSK_ERR_ARG for hits without weights
+        uint64_t nq = 0, nh = 0;
+        int rc = bsk_hits_info(p_, &nq, &nh);
+        if (rc != BSK_OK) return rc;
+        dot.assign(nh + 1, 0);
+        min_sum.assign(nh + 1, 0);
+        rc = bsk_hits_fetch_weights(e.ctx(), p_, 0, nq, dot.data(), min_sum.data(), nh + 1);
+        dot.resize(nh);
+        min_sum.resize(nh);
+        return rc;
+    }
 };
 
 // sparse all-pairs comparison (bsk_sets_neighbors): per set of a the sets of b that pass np (nullptr: every pair that shares a value),
@@ -415,6 +435,11 @@ class SearchHits : public Owned<bsk_hits, bsk_hits_release> {
 // totals; no matrix is stored and the number of cells is not limited.
 inline int DeviceSets::neighbors(Engine &e, const DeviceSets &b, uint64_t limit, const bsk_neighbor_params *np, SearchHits &into) const {
     return bsk_sets_neighbors(e.ctx(), p_, b.get(), limit, np, &into.handle());
+}
+// bsk_sets_neighbors_counted: neighbors() with the counts of SetsCompare::compare_counted -- the same hits, which also carry weights
+// (SearchHits::weights_device, fetch_weights); np reads shared and total only
+inline int DeviceSets::neighbors_counted(Engine &e, const DeviceSets &b, uint64_t limit, const bsk_neighbor_params *np, SearchHits &into) const {
+    return bsk_sets_neighbors_counted(e.ctx(), p_, b.get(), limit, np, &into.handle());
 }
 
 // inverted index of target sets (bsk_index)

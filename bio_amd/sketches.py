@@ -470,6 +470,16 @@ class Sets(_Owner):
         compared exactly, or a float x in 0..1 taken as (ceil(x * 2^30), 2^30).  upper: only pairs with j > i (self against itself:
         every unordered pair once, the lower triangle never computed).  -> Hits with .total; any number of cells.  reuse: any Hits
         of this engine, whose device arrays are kept."""
+        return self._neighbors(other, limit, min_shared, min_jaccard, upper, reuse, False)
+
+    def neighbors_counted(self, other: Optional["Sets"] = None, limit: int = 0, min_shared: int = 1, min_jaccard=None, upper: bool = False,
+                          reuse: Optional["Hits"] = None) -> "Hits":
+        """neighbors() with the counts (bsk_sets_neighbors_counted): the same pairs, offsets, targets, shared and totals -- the
+        thresholds read shared and total only -- and per kept pair .dot and .min_sum as compare_counted() defines them.  Sets without
+        counts count 1 for every value.  The Hits keep both operands for their norms (cosine() and its kin)."""
+        return self._neighbors(other, limit, min_shared, min_jaccard, upper, reuse, True)
+
+    def _neighbors(self, other, limit, min_shared, min_jaccard, upper, reuse, counted):
         other = self if other is None else other
         num, den = 0, 0
         if min_jaccard is not None:
@@ -481,9 +491,10 @@ class Sets(_Owner):
                     raise ValueError("min_jaccard outside 0..1")
                 num, den = int(math.ceil(x * (1 << 30))), 1 << 30
         np_ = L.NeighborParams(min_shared, L.NEIGHBORS_UPPER if upper else 0, num, den)
-        h = _take_over(self.eng, reuse, lambda out: self.eng.lib.bsk_sets_neighbors(self.eng.ctx, self.h, other.h, limit, C.byref(np_), out))
+        entry = self.eng.lib.bsk_sets_neighbors_counted if counted else self.eng.lib.bsk_sets_neighbors
+        h = _take_over(self.eng, reuse, lambda out: entry(self.eng.ctx, self.h, other.h, limit, C.byref(np_), out))
         res = reuse if reuse is not None else Hits(self.eng)
-        res._bind(h, np.diff(self.offsets()), np.diff(other.offsets()))
+        res._bind(h, np.diff(self.offsets()), np.diff(other.offsets()), (self, other, limit) if counted else None)
         return res
 
     def plan(self):
@@ -685,13 +696,15 @@ class Hits(_Owner):
 
     _release = "bsk_hits_release"
     _totals = None  # total[] of hits with totals (Sets.neighbors), fetched with the others
+    _weights = _norms = _operands = None  # the weighted side (Sets.neighbors_counted): (dot, min_sum), fetched with the others; (sumsq_a, sumsq_b, totals_a, totals_b); (a, b, limit)
 
     def __init__(self, eng: "Engine"):
         self.eng, self.h = eng, None
         self._host = None
 
-    def _bind(self, h, query_sizes: np.ndarray, target_sizes: np.ndarray):
+    def _bind(self, h, query_sizes: np.ndarray, target_sizes: np.ndarray, operands=None):
         self.h, self._host, self._totals = h, None, None
+        self._weights, self._norms, self._operands = None, None, operands
         self.query_sizes, self.target_sizes = query_sizes.astype(np.uint64), target_sizes
 
     def info(self):
@@ -771,10 +784,30 @@ class Hits(_Owner):
         self.eng._chk(self.eng.lib.bsk_hits_fetch_totals(self.eng.ctx, self.h, first, count, tt.ctypes.data, tt.size))
         return tt[:int(offs[-1])]
 
+    def has_weights(self) -> bool:
+        """whether the last entry that wrote these hits kept dot and min_sum (bsk_hits_weights_device gives arrays): Sets.neighbors_counted does"""
+        if not self.h:
+            return self._weights is not None
+        pd, pm = C.c_void_p(), C.c_void_p()
+        self.eng._chk(self.eng.lib.bsk_hits_weights_device(self.h, C.byref(pd), C.byref(pm)))
+        return bool(pd.value) and bool(pm.value)
+
+    def fetch_weights(self, first: int = 0, count: Optional[int] = None):
+        """bsk_hits_fetch_weights -> (dot[], min_sum[]) u64 of the hits of the range; hits without weights raise"""
+        inf = self.info()
+        if count is None:
+            count = inf["n_queries"] - first
+        dt, ms = np.zeros(max(inf["n_hits"], 1), np.uint64), np.zeros(max(inf["n_hits"], 1), np.uint64)
+        offs = np.zeros(count + 1, np.uint64)
+        self.eng._chk(self.eng.lib.bsk_hits_fetch(self.eng.ctx, self.h, first, count, offs.ctypes.data, None, None, 0))
+        self.eng._chk(self.eng.lib.bsk_hits_fetch_weights(self.eng.ctx, self.h, first, count, dt.ctypes.data, ms.ctypes.data, dt.size))
+        return dt[:int(offs[-1])], ms[:int(offs[-1])]
+
     def _cache(self):
         if self._host is None:
             self._host = self.fetch()
             self._totals = self.fetch_totals() if self.has_totals() else None
+            self._weights = self.fetch_weights() if self.has_weights() else None
         return self._host
 
     @property
@@ -794,6 +827,19 @@ class Hits(_Owner):
         """per hit the values walked (min(limit, |a | b|)); None for hits without totals (a search, top())"""
         self._cache()
         return self._totals
+
+    @property
+    def dot(self) -> Optional[np.ndarray]:
+        """per hit the sum of the products of the two counts over the walked values both sets hold (u64, saturating); None for hits
+        without weights (anything but Sets.neighbors_counted)"""
+        self._cache()
+        return None if self._weights is None else self._weights[0]
+
+    @property
+    def min_sum(self) -> Optional[np.ndarray]:
+        """per hit the sum of the minima of the two counts (u64, exact); None for hits without weights"""
+        self._cache()
+        return None if self._weights is None else self._weights[1]
 
     def query(self) -> np.ndarray:
         """the query index of every hit"""
@@ -821,6 +867,54 @@ class Hits(_Owner):
         nz = j > 0
         d[nz] = np.maximum(0.0, -np.log(2.0 * j[nz] / (1.0 + j[nz])) / k)
         return d
+
+
+    # -- the weighted side (bsk_sets_neighbors_counted): Compare's formulas, per hit
+    def _whole(self, what: str):
+        """(dot, min_sum, sumsq_a, sumsq_b, totals_a, totals_b) per hit of weighted hits over whole sets: the norms of the two operands
+        gathered by query() and target"""
+        self._cache()
+        if self._weights is None:
+            raise ValueError("hits without weights: use Sets.neighbors_counted")
+        if self._norms is None:
+            a, b, limit = self._operands
+            if limit != 0:
+                raise ValueError(what + " is defined on whole sets: neighbors_counted with limit=0")
+            qa, ta = a.sumsq(), a.totals()
+            qb, tb = (qa, ta) if b is a else (b.sumsq(), b.totals())
+            self._norms = (qa, qb, ta, tb)
+        qa, qb, ta, tb = self._norms
+        i, j = self.query().astype(np.int64), self.target.astype(np.int64)
+        return self._weights[0], self._weights[1], qa[i], qb[j], ta[i], tb[j]
+
+    def cosine(self) -> np.ndarray:
+        """per hit dot / (sqrt(sumsq_a[i]) * sqrt(sumsq_b[j])) as float64: 0.0 where a norm is 0, NaN where dot or either norm is saturated"""
+        dt, _, qa, qb, _, _ = self._whole("cosine")
+        top = int(np.iinfo(np.uint64).max)
+        den = np.sqrt(qa.astype(np.float64)) * np.sqrt(qb.astype(np.float64))
+        cos = np.divide(dt.astype(np.float64), den, out=np.zeros(dt.shape, np.float64), where=den != 0)
+        cos[(dt == top) | (qa == top) | (qb == top)] = np.nan
+        return cos
+
+    def angular_similarity(self) -> np.ndarray:
+        """per hit 1 - 2 acos(min(cosine, 1)) / pi: what sourmash compare reports for signatures with abundance"""
+        return 1.0 - 2.0 * np.arccos(np.minimum(self.cosine(), 1.0)) / np.pi
+
+    def weighted_jaccard(self) -> np.ndarray:
+        """per hit min_sum / (totals_a[i] + totals_b[j] - min_sum) -- the sum of minima over the sum of maxima -- 0.0 where that is 0"""
+        _, ms, _, _, ta, tb = self._whole("weighted_jaccard")
+        m = ms.astype(np.float64)
+        den = ta.astype(np.float64) + tb.astype(np.float64) - m
+        return np.divide(m, den, out=np.zeros_like(m), where=den != 0)
+
+    def bray_curtis(self) -> np.ndarray:
+        """per hit 1 - 2 min_sum / (totals_a[i] + totals_b[j]) (the dissimilarity), 0.0 where the denominator is 0"""
+        _, ms, _, _, ta, tb = self._whole("bray_curtis")
+        m = ms.astype(np.float64)
+        den = ta.astype(np.float64) + tb.astype(np.float64)
+        out, nz = np.zeros_like(m), den != 0
+        out[nz] = 1.0 - 2.0 * m[nz] / den[nz]
+        return out
 
 
 class Clusters(_Owner):

@@ -491,8 +491,8 @@ int bsk_result_sets(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk
  *     BSK_ERR_NOMEM and BSK_ERR_DEVICE release.
  *   bsk_sets_compare, _compare_counted: every BSK_ERR_ARG keeps the slot; both size limits (BSK_ERR_UNSUPPORTED) are checked after the
  *     object is taken over and release it, as BSK_ERR_NOMEM and BSK_ERR_DEVICE do.
- *   bsk_sets_neighbors: as bsk_sets_compare -- every BSK_ERR_ARG keeps the slot, its size limits (BSK_ERR_UNSUPPORTED), BSK_ERR_NOMEM and
- *     BSK_ERR_DEVICE release.
+ *   bsk_sets_neighbors, _neighbors_counted: as bsk_sets_compare -- every BSK_ERR_ARG keeps the slot, its size limits
+ *     (BSK_ERR_UNSUPPORTED), BSK_ERR_NOMEM and BSK_ERR_DEVICE release.
  *   bsk_hits_cluster (bsk_clusters **out) and bsk_hits_from_host: every BSK_ERR_ARG and the 2^32 limits keep the slot; BSK_ERR_NOMEM and
  *     BSK_ERR_DEVICE release.
  *   bsk_result_sets_reuse, _counted: a NULL `sets` and sets of another context (BSK_ERR_ARG) keep the slot.  Every other error releases:
@@ -788,6 +788,34 @@ void bsk_clusters_release(bsk_clusters *c);
 int bsk_hits_from_host(bsk_ctx *ctx, const uint64_t *offsets, uint64_t n_queries, const uint32_t *target, const uint32_t *shared,
                        const uint32_t *total /* NULL: hits without totals */, bsk_hits **hits);
 
+/* ---- weighted sparse all-pairs comparison: dot and min_sum per kept neighbour ----
+ * (bsk_neighbor_params and BSK_NEIGHBORS_UPPER are defined in the block below, which closes the header; nothing here adds a flag or a struct.)
+ * bsk_sets_neighbors_counted is bsk_sets_neighbors with the counts of bsk_sets_compare_counted.  The walk, the rule and the result layout
+ * are exactly those of bsk_sets_neighbors: offsets, target, shared and total are bit-identical to what bsk_sets_neighbors gives for the
+ * same operands, limit and params.  Weights are a payload; they do not take part in the rule -- no threshold reads them.
+ * The hits also carry two u64 device arrays parallel to target[]: dot[n_hits] and min_sum[n_hits], defined exactly as the cells of
+ * bsk_sets_compare_counted -- over the walked values that both sets hold, dot is the saturating sum of the count products (capped at
+ * 2^64-1) and min_sum the exact sum of the minima.  An uncounted operand counts 1 per value; with both operands uncounted
+ * dot == min_sum == shared.  With the norms of the operands (bsk_sets_sumsq, bsk_sets_totals) they give the cosine, the weighted Jaccard
+ * and the Bray-Curtis dissimilarity of every kept pair (formulas: bsk_sets_compare_counted), without a matrix.
+ * The limits (2^32 values together, 2^32 sets each, 2^32 kept pairs, NO limit on cells), a == b and BSK_NEIGHBORS_UPPER -- tiles below
+ * the diagonal are never run --, empty operands, the *hits rules ("The result slot" above) and the order of the argument checks (null,
+ * flag, fraction, foreign context) are those of bsk_sets_neighbors.
+ * Re-use: *hits may be any bsk_hits of this context.  The object remembers whether its last writer kept weights: bsk_index_search,
+ * bsk_hits_top, the pipeline's hits sink, bsk_hits_from_host and the unweighted bsk_sets_neighbors leave it without weights and keep the
+ * two arrays, which only grow.  bsk_hits_info / _fetch / _totals_device / _fetch_totals / _top / _cluster / _release work unchanged on
+ * weighted hits; the output of bsk_hits_top carries neither totals nor weights.
+ * bsk_hits_weights_device: both NULL for hits without weights.  bsk_hits_fetch_weights: the weights of the hits of rows first ..
+ * first + count - 1, with the range, cap and foreign-context rules of bsk_hits_fetch_totals; BSK_ERR_ARG for hits without weights.
+ * bsk_hits_plan names the kernel (k_cmp_tile_nb_w) and carries the same tiles=, skipped=, rounds= and runs= figures; a kept pair takes
+ * 32 bytes of the record buffer instead of 16.  The result is bit-identical from call to call. */
+struct bsk_neighbor_params;   /* defined in the block below */
+int bsk_sets_neighbors_counted(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, uint64_t limit,
+                               const struct bsk_neighbor_params *np /* NULL: {1,0,0,0} */, bsk_hits **hits);
+int bsk_hits_weights_device(const bsk_hits *h, const uint64_t **dot, const uint64_t **min_sum);   /* either may be NULL; both NULL for hits without weights */
+int bsk_hits_fetch_weights(bsk_ctx *ctx, const bsk_hits *h, uint64_t first, uint64_t count,
+                           uint64_t *dot, uint64_t *min_sum, uint64_t hit_cap);                     /* either array may be NULL */
+
 /* ---- sparse all-pairs comparison: the neighbours above a threshold, no matrix ----
  * bsk_sets_neighbors walks every pair (i, j), i < n_a, j < n_b, exactly as bsk_sets_compare does -- the first `limit` distinct values of
  * a[i] | b[j], ascending (limit == 0: all of them; any u64 is a legal limit) -- so shared and total of a pair are what bsk_sets_compare
@@ -818,8 +846,10 @@ int bsk_hits_from_host(bsk_ctx *ctx, const uint64_t *offsets, uint64_t n_queries
  * Which route for an all-against-all: bsk_sets_compare when every cell is wanted and there are at most 2^31 of them;
  * bsk_sets_neighbors when only the pairs above a threshold are (dereplication, clustering, nearest references, the k nearest
  * neighbours), limit-bounded (Mash) numbers included, at any number of cells -- its cost is still the cells (half of them with
- * BSK_NEIGHBORS_UPPER) times the values a pair walks; bsk_index_build + bsk_index_search for whole sets (limit == 0 only) of many values
- * of which most pairs share nothing -- its cost follows the postings. */
+ * BSK_NEIGHBORS_UPPER) times the values a pair walks; bsk_sets_neighbors_counted (declared above this block) is the same route
+ * with dot and min_sum of every kept pair, for abundance-weighted measures beyond the dense compare's 2^31 cells;
+ * bsk_index_build + bsk_index_search for whole sets (limit == 0 only) of many values of which most pairs share nothing -- its
+ * cost follows the postings. */
 enum { BSK_NEIGHBORS_UPPER = 1 };            /* list only pairs with j > i */
 typedef struct bsk_neighbor_params {
     uint32_t min_shared;    /* 0 is taken as 1 */
