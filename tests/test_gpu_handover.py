@@ -1,9 +1,9 @@
-"""The in/out object slot of the sets-side entries (bsk_sets **out, bsk_hits **hits, bsk_compare **cmp; host_types.hpp: take_over;
+"""The in/out object slot of the sets-side entries (bsk_sets **out, bsk_hits **hits, bsk_compare **cmp, bsk_clusters **out; host_types.hpp: take_over;
 include/biosketch.h "The result slot"), entry by entry through raw ctypes on ONE context, on 3 sets of at most 5 values:
 
   1. an empty slot yields an object; the same call with that object in the slot yields the same handle and the same device pointers;
   2. an argument error the entry checks BEFORE it takes the slot over -- a bad op, n == 0, min_members == 0, min_count == 0, *out equal
-     to the input, reserved != 0; for the two compares, whose checks of that kind are the null and the context ones only, a null `b` --
+     to the input, reserved != 0, an unknown flag of the neighbours, a host row that does not ascend, an unknown cluster method; for the two compares, whose checks of that kind are the null and the context ones only, a null `b` --
      returns BSK_ERR_ARG, leaves the handle where it is and the earlier result's contents intact;
   3. an object of ANOTHER context in the slot (made by a second engine on the same device; of the slot's own type) returns BSK_ERR_ARG
      and is left alone.  For bsk_result_sets_reuse / _counted this is the only error a re-used slot survives;
@@ -20,9 +20,12 @@ import numpy as np
 import pytest
 
 from bio_amd import _lib as L
+from tests import cluster_cases as CL
 from tests import compare_cases as CM
 from tests import compare_counted_cases as CW
 from tests import counts_cases as CC
+from tests import neighbor_cases as NC
+from tests import neighbor_counted_cases as NW
 from tests import search_cases as SR
 from tests import setops_cases as SO
 from tests import sets_cases as SC
@@ -34,7 +37,8 @@ SETS = ("bsk_sets_op", "bsk_sets_op_counted", "bsk_sets_reduce", "bsk_sets_filte
 COMPARES = ("bsk_sets_compare", "bsk_sets_compare_counted")
 SEARCHES = ("bsk_index_search", "bsk_hits_top")
 RESULTS = ("bsk_result_sets_reuse", "bsk_result_sets_counted")
-ENTRIES = SETS + COMPARES + SEARCHES + RESULTS
+GRAPHS = ("bsk_sets_neighbors", "bsk_sets_neighbors_counted", "bsk_hits_from_host", "bsk_hits_cluster")
+ENTRIES = SETS + COMPARES + SEARCHES + RESULTS + GRAPHS
 
 
 def fetch_sets(eng, h):
@@ -54,13 +58,30 @@ def sets_ptrs(eng, h):
 
 
 def fetch_hits(eng, h):
+    """(offsets, target, shared) and, where the hits carry them, (total,) and (dot, min_sum) behind them"""
     from bio_amd import sketches as S
     x = S.Hits(eng)
+    x.h = h
+    try:
+        return x.fetch() + ((x.fetch_totals(),) if x.has_totals() else ()) + (x.fetch_weights() if x.has_weights() else ())
+    finally:
+        x.h = None
+
+
+def fetch_clusters(eng, h):
+    from bio_amd import sketches as S
+    x = S.Clusters(eng)
     x.h = h
     try:
         return x.fetch()
     finally:
         x.h = None
+
+
+def clusters_ptrs(eng, h):
+    p = [C.c_void_p() for _ in range(4)]
+    assert eng.lib.bsk_clusters_device(h, *[C.byref(x) for x in p]) == L.OK
+    return tuple(x.value for x in p)
 
 
 def hits_ptrs(eng, h):
@@ -91,6 +112,7 @@ KINDS = {  # what a slot holds -> (fetch, device pointers, the release function'
     "sets": (fetch_sets, sets_ptrs, "bsk_sets_release"),
     "hits": (fetch_hits, hits_ptrs, "bsk_hits_release"),
     "compare": (fetch_compare, compare_ptrs, "bsk_compare_release"),
+    "clusters": (fetch_clusters, clusters_ptrs, "bsk_clusters_release"),
 }
 
 
@@ -130,6 +152,11 @@ def world(oracle):
     f_batch = other.batch(reads)
     foreign = NS(sets=f_sets, compare=f_sets.compare(), hits=f_sets.index().search(f_sets), result=other.run(f_batch, other.params(L.KMER, K)),
                  want=dict(sets=ha + (None,), compare=CM.ref_compare(A, A, 0), hits=SR.ref_search(ha[0], ha[1], ha[0], ha[1])))
+    foreign.clusters = foreign.hits.cluster()
+    foreign.want["clusters"] = CL.model_components(3, *foreign.want["hits"][:2])[:4]
+    flag_np, cl_bad = L.NeighborParams(1, 2, 0, 0), L.ClusterParams(7, 0)  # (an unknown flag bit; an unknown method)
+    g_offs, g_tgt, g_sh, g_tot = np.array([0, 2, 2, 3], U64), np.array([0, 2, 1], U32), np.array([4, 5, 6], U32), np.array([7, 8, 9], U32)
+    g_unsorted = np.array([2, 0, 1], U32)
     by = lambda out: C.byref(out)
     e = {
         "bsk_sets_op": NS(kind="sets", good=lambda o: lib.bsk_sets_op(ctx, sa.h, sb.h, L.SETOP_UNION, by(o)), want=SO.ref_op(ha, hb, SO.UNION) + (None,),
@@ -154,10 +181,20 @@ def world(oracle):
                                     bad=[], scope=lambda o: lib.bsk_result_sets_reuse(ctx, result.h, 2, 1, by(o))),
         "bsk_result_sets_counted": NS(kind="sets", good=lambda o: lib.bsk_result_sets_counted(ctx, result.h, L.SETS_PER_SEQUENCE, 1, by(o)), want=CC.ref_counted(per, 1, False),
                                       bad=[], scope=lambda o: lib.bsk_result_sets_counted(ctx, result.h, 2, 1, by(o))),
+        "bsk_sets_neighbors": NS(kind="hits", good=lambda o: lib.bsk_sets_neighbors(ctx, sa.h, sb.h, 0, None, by(o)), want=NC.ref_neighbors(A, B, 0),
+                                 bad=[lambda o: lib.bsk_sets_neighbors(ctx, sa.h, sb.h, 0, by(flag_np), by(o))]),
+        "bsk_sets_neighbors_counted": NS(kind="hits", good=lambda o: lib.bsk_sets_neighbors_counted(ctx, sca.h, scb.h, 0, None, by(o)),
+                                         want=NW.filter_weighted(*CW.ref_compare(A, CA, B, CB, 0)),
+                                         bad=[lambda o: lib.bsk_sets_neighbors_counted(ctx, sca.h, scb.h, 0, by(flag_np), by(o))]),
+        "bsk_hits_from_host": NS(kind="hits", good=lambda o: lib.bsk_hits_from_host(ctx, g_offs.ctypes.data, 3, g_tgt.ctypes.data, g_sh.ctypes.data, g_tot.ctypes.data, by(o)),
+                                 want=(g_offs, g_tgt, g_sh, g_tot),
+                                 bad=[lambda o: lib.bsk_hits_from_host(ctx, g_offs.ctypes.data, 3, g_unsorted.ctypes.data, g_sh.ctypes.data, g_tot.ctypes.data, by(o))]),
+        "bsk_hits_cluster": NS(kind="clusters", good=lambda o: lib.bsk_hits_cluster(ctx, hits.h, None, None, by(o)), want=CL.model_components(3, *want_hits[:2])[:4],
+                               bad=[lambda o: lib.bsk_hits_cluster(ctx, hits.h, by(cl_bad), None, by(o))]),
     }
     assert tuple(e) == ENTRIES
     yield NS(eng=eng, other=other, entries=e, foreign=foreign, result=result)
-    for x in (foreign.sets, foreign.compare, foreign.hits, foreign.result, f_batch, hits, index, sa, sb, sca, scb, result, batch):
+    for x in (foreign.clusters, foreign.sets, foreign.compare, foreign.hits, foreign.result, f_batch, hits, index, sa, sb, sca, scb, result, batch):
         x.close()
     other.close()
     eng.close()
@@ -186,7 +223,7 @@ def test_empty_slot_then_the_same_object(world, name):
         release(slot)
 
 
-@pytest.mark.parametrize("name", SETS + COMPARES + SEARCHES)
+@pytest.mark.parametrize("name", SETS + COMPARES + SEARCHES + GRAPHS)
 def test_argument_error_keeps_the_slot(world, name):
     e, slot, fetch, ptrs, release = made(world, name)
     try:
