@@ -74,6 +74,16 @@ class ClusterParams(C.Structure):
     _fields_ = [("method", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class WindowParams(C.Structure):
+    """bsk_window_params (include/biosketch.h)"""
+    _fields_ = [("window", C.c_uint32), ("step", C.c_uint32), ("count", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class FoldParams(C.Structure):
+    """bsk_fold_params (include/biosketch.h)"""
+    _fields_ = [("min_members", C.c_uint32), ("flags", C.c_uint32), ("frac_num", C.c_uint32), ("frac_den", C.c_uint32)]
+
+
 class SearchParams(C.Structure):
     """bsk_search_params (include/biosketch.h)"""
     _fields_ = [("min_shared", C.c_uint32), ("reserved", C.c_uint32), ("min_query_cov", C.c_double), ("min_target_cov", C.c_double)]
@@ -213,7 +223,12 @@ SYMBOLS = [
     ("bsk_clusters_device", C.c_int, [_vp, _pp, _pp, _pp, _pp]),
     ("bsk_clusters_release", None, [_vp]),
     ("bsk_hits_from_host", C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _pp]),
+    ("bsk_result_sets_windows", C.c_int, [_vp, _vp, C.POINTER(WindowParams), C.c_int, _pp, _vp]),
+    ("bsk_hits_fold", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(FoldParams), _pp]),
+    ("bsk_hits_members_device", C.c_int, [_vp, _pp]),
+    ("bsk_hits_fetch_members", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64]),
 ]
+WINDOWS_COUNTED = 1
 NEIGHBORS_UPPER = 1
 CLUSTER_COMPONENTS, CLUSTER_GREEDY = 0, 1
 SETS_PER_SEQUENCE, SETS_WHOLE_BATCH = 0, 1

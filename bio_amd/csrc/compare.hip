@@ -769,6 +769,7 @@ int neighbors_impl(bsk_ctx *ctx, const bsk_sets *a, const bsk_sets *b, u64 limit
     res->n_large = 0;
     res->has_total = false;
     res->has_weights = false;  // (an unweighted call into weighted hits keeps the two arrays)
+    res->has_members = false;  // (neighbours carry no members)
     HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (n_a + 1) * 8));
     if (n_a == 0 || n_b == 0) {
         HIPCHK(ctx, hipMemsetAsync(res->offsets, 0, (n_a + 1) * 8, st));

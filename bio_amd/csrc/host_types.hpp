@@ -72,7 +72,11 @@ enum PoolSlot {
     SLOT_CLUSTER_NODES = 48, SLOT_CLUSTER_EDGES = 49, SLOT_CLUSTER_SORT = 50,
     // weighted sparse all-pairs comparison (compare.hip): the kept pairs' (dot, min_sum), slot for slot beside SLOT_NB_RECORDS
     SLOT_NB_WEIGHTS = 51,
-    POOL_SLOTS = 52
+    // window sets (windows.hip): the per-sequence window counts, lengths and offsets; the windows' spans, which sets_build reads as its source
+    SLOT_WIN_SEQS = 52, SLOT_WIN_SPANS = 53,
+    // folded hits (fold.hip): the target-to-group map; the group offsets, heads, runs and their scans
+    SLOT_FOLD_MAP = 54, SLOT_FOLD_WORK = 55,
+    POOL_SLOTS = 56
 };
 
 struct bsk_ctx {

@@ -726,6 +726,7 @@ extern "C" void bsk_hits_release(bsk_hits *h) {
     (void)hipFree(h->total);
     (void)hipFree(h->dot);
     (void)hipFree(h->msum);
+    (void)hipFree(h->members);
     delete h;
 }
 
@@ -751,6 +752,7 @@ extern "C" int bsk_hits_from_host(bsk_ctx *ctx, const uint64_t *offsets, uint64_
         res->n_large = 0;
         res->has_total = false;
         res->has_weights = false;
+        res->has_members = false;
         HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (n_queries + 1) * 8));
         HIPCHK(ctx, grow_array(&res->target, &res->c_target, (H ? H : 1) * 4));
         HIPCHK(ctx, grow_array(&res->shared, &res->c_shared, (H ? H : 1) * 4));
@@ -794,6 +796,7 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
     res->n_large = 0;
     res->has_total = false;  // (a search into hits with totals keeps the array, like a counted bsk_sets written by an uncounted entry)
     res->has_weights = false;  // (... and so for the weights)
+    res->has_members = false;  // (... and the members of folded hits)
     HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (nq + 1) * 8));
     // per-query arrays (one carved buffer) and the query values' posting ranges
     Carve cq;
@@ -900,6 +903,7 @@ static int top_impl(bsk_ctx *ctx, const bsk_hits *h, u32 n, bsk_hits *res) {
     res->n_large = 0;
     res->has_total = false;  // the n best carry no totals
     res->has_weights = false;  // ... and no weights
+    res->has_members = false;  // ... and no members
     HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (nq + 1) * 8));
     // scratch: the search's own slots (its temporaries are dead once its hits exist)
     Carve cq;

@@ -24,6 +24,11 @@ struct bsk_hits {
     u64 *dot = nullptr, *msum = nullptr;  // [n_hits]
     size_t c_dot = 0, c_msum = 0;
     bool has_weights = false;
+    // folded hits (fold.hip: bsk_hits_fold): members[i] = how many targets of hit i's group the row hit.  `has_members` follows the rule of
+    // `has_total` too: whoever clears that clears this, and the array stays.
+    u32 *members = nullptr;  // [n_hits]
+    size_t c_members = 0;
+    bool has_members = false;
 };
 
 // clusters of a hits graph (cluster.hip: bsk_hits_cluster)

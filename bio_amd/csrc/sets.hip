@@ -561,14 +561,11 @@ extern "C" void bsk_sets_release(bsk_sets *s) {
     delete s;
 }
 
-namespace {
-// What the three entries below run on the object take_over hands them.  `reused`: an earlier result's arrays, which grow with slack (a
-// fresh object gets exactly what it needs).  Every failure in here releases the object and leaves the slot NULL.
-int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool counted, bsk_sets *res, bool reused) {
-    if (!ctx || !r) return fail_arg(ctx, counted ? "bsk_result_sets_counted: null argument" : "bsk_result_sets: null argument");
-    if (r->ctx != ctx || (scope != BSK_SETS_PER_SEQUENCE && scope != BSK_SETS_WHOLE_BATCH) || scale < 0)
-        return fail_arg(ctx, r->ctx != ctx ? "bsk_result_sets: result belongs to another context" : scale < 0 ? "bsk_result_sets: bad scale" : "bsk_result_sets: bad scope");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail_arg(ctx, "bsk_result_sets: hipSetDevice");
+// What the entries that make sets from tuples run on the object take_over hands them: the sets of a span source (sets_internal.hpp) -- a
+// result's own sequences (sets_build below) or the windows of its sequences (windows.hip).  `reused`: an earlier result's arrays, which
+// grow with slack (a fresh object gets exactly what it needs).  Every failure in here releases the object and leaves the slot NULL.
+int sets_build_spans(bsk_ctx *ctx, const SpanSrc &src, int scope, int scale, bool counted, bsk_sets *res, bool reused) {
+    const SpanSrc *r = &src;
     const u64 n = r->n;
     const u64 maxhash = scale > 1 ? ~0ULL / (u64)scale : ~0ULL;
     const u64 n_sets = scope == BSK_SETS_WHOLE_BATCH ? 1 : n;
@@ -588,7 +585,7 @@ int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool cou
     const u64 max_count = ctx->h_pinned[0], N = ctx->h_pinned[1];
     size_t tb = 0;
     if (N >= (1ULL << 32)) {
-        ctx->err = "bsk_result_sets: more than 2^32 values in one call (split the batch)";
+        ctx->err = std::string(src.entry) + ": more than 2^32 values in one call (split the batch)";
         return BSK_ERR_UNSUPPORTED;
     }
     res->n_sets = n_sets;
@@ -674,6 +671,15 @@ int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool cou
     return BSK_OK;
 }
 
+namespace {
+// What the three entries below run: their checks, then sets_build_spans over the result's own arrays -- a sequence is a span.
+int sets_build(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bool counted, bsk_sets *res, bool reused) {
+    if (!ctx || !r) return fail_arg(ctx, counted ? "bsk_result_sets_counted: null argument" : "bsk_result_sets: null argument");
+    if (r->ctx != ctx || (scope != BSK_SETS_PER_SEQUENCE && scope != BSK_SETS_WHOLE_BATCH) || scale < 0)
+        return fail_arg(ctx, r->ctx != ctx ? "bsk_result_sets: result belongs to another context" : scale < 0 ? "bsk_result_sets: bad scale" : "bsk_result_sets: bad scope");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_arg(ctx, "bsk_result_sets: hipSetDevice");
+    return sets_build_spans(ctx, SpanSrc{r->hash, r->refs, r->wfirst, r->wcount, r->n, "bsk_result_sets"}, scope, scale, counted, res, reused);
+}
 }  // namespace
 
 extern "C" int bsk_result_sets(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk_sets **out) {

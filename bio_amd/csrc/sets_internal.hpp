@@ -25,6 +25,19 @@ struct bsk_sets {
     bool counted = false;
 };
 
+// What sets_build_spans (sets.hip) makes sets from: n spans of tuples of one hash array, one set per span (or one set of all of them).
+// Span i is a packed reference word refs[i] -- (first_tuple << 24) | n_tuples, bit 63 = the tuples are 64 apart -- or, with refs == NULL,
+// wfirst[i] / wcount[i] with stride 1: the two forms a bsk_result describes its sequences in.  Spans may overlap (windows.hip).
+struct SpanSrc {
+    const u64 *hash, *refs, *wfirst, *wcount;
+    u64 n;
+    const char *entry;  // the C entry's name, for the error text
+};
+// The sets of the spans into `res` (the object take_over handed to the entry; `reused`: its arrays grow with slack): the dense copy, the
+// small-set path or the segmented sort, the FracMinHash filter and, with `counted`, the run lengths.  Every failure leaves `res` to be
+// released by the caller's take_over.
+int sets_build_spans(bsk_ctx *ctx, const SpanSrc &src, int scope, int scale, bool counted, bsk_sets *res, bool reused) __attribute__((visibility("hidden")));
+
 // counts.hip: run lengths of the kept heads of a sorted, flagged array (what sets.hip's general path has after its scan).  keep[i] = 1
 // marks a kept head, pos[i] its place in the output; a run ends at the next kept head, at the first value above maxhash (filt) or at n.
 // part: sets_run_counts_parts(n) u64 of scratch.  All on `st`, nothing read back.

@@ -212,6 +212,13 @@ class DeviceSets : public Owned<bsk_sets, bsk_sets_release> {
     // ---- counted sets: values with their abundance (counts[i] belongs to values[i]) ----
     // the counted sets of a result INTO this object (empty, or any sets of this engine: arrays kept, grow only)
     int from_result_counted(Engine &e, const bsk_result *r, int scope, int scale = 1) { return bsk_result_sets_counted(e.ctx(), r, scope, scale, &p_); }
+    // one set per window of every sequence's positions (bsk_result_sets_windows) INTO this object: wp.window / wp.step, or wp.count windows
+    // per sequence; seq_offsets[n_reads + 1] receives where every sequence's windows start (the group offsets of reduce and SearchHits::fold)
+    int from_windows(Engine &e, const bsk_result *r, const bsk_window_params &wp, int scale, std::vector<uint64_t> *seq_offsets = nullptr) {
+        uint64_t n = 0;
+        if (seq_offsets && bsk_result_info(r, &n, nullptr, nullptr) == BSK_OK) seq_offsets->assign(n + 1, 0);
+        return bsk_result_sets_windows(e.ctx(), r, &wp, scale, &p_, seq_offsets ? seq_offsets->data() : nullptr);
+    }
     int from_host_counted(Engine &e, const std::vector<uint64_t> &offsets, const std::vector<uint64_t> &values, const std::vector<uint32_t> &counts) {
         if (offsets.empty() || offsets.back() != values.size() || counts.size() != values.size()) return BSK_ERR_ARG;
         bsk_sets_release(p_);
@@ -396,6 +403,26 @@ class SearchHits : public Owned<bsk_hits, bsk_hits_release> {
     // every query's min(n, hits) best hits, largest shared count first, ties by ascending target (bsk_hits_top); into: empty, or the
     // result of an earlier top on this engine (its device arrays are kept and only grow)
     int top(Engine &e, uint32_t n, SearchHits &into) const { return bsk_hits_top(e.ctx(), p_, n, &into.handle()); }
+    // the hits summed by target group (bsk_hits_fold): group g is targets group_offsets[g] .. group_offsets[g + 1] - 1; fp: nullptr keeps every
+    // group with a hit; into: empty, or any hits of this engine but this object.  The result carries members (members_device, fetch_members)
+    int fold(Engine &e, const std::vector<uint64_t> &group_offsets, const bsk_fold_params *fp, SearchHits &into) const {
+        if (group_offsets.empty()) return BSK_ERR_ARG;
+        return bsk_hits_fold(e.ctx(), p_, group_offsets.data(), group_offsets.size() - 1, fp, &into.handle());
+    }
+    const uint32_t *members_device() const {  // nullptr for hits without members
+        const uint32_t *m = nullptr;
+        bsk_hits_members_device(p_, &m);
+        return m;
+    }
+    int fetch_members(Engine &e, std::vector<uint32_t> &members) const {  // BSK_ERR_ARG for hits without members
+        uint64_t nq = 0, nh = 0;
+        int rc = bsk_hits_info(p_, &nq, &nh);
+        if (rc != BSK_OK) return rc;
+        members.assign(nh + 1, 0);
+        rc = bsk_hits_fetch_members(e.ctx(), p_, 0, nq, members.data(), nh + 1);
+        members.resize(nh);
+        return rc;
+    }
     // hits with totals (DeviceSets::neighbors): the device array total[n_hits], nullptr for the hits of a search or of top()
     const uint32_t *totals_device() const {
         const uint32_t *t = nullptr;

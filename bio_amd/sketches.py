@@ -286,7 +286,23 @@ class BatchResult(_Owner):
         self.eng._opts()
         scope = L.SETS_WHOLE_BATCH if whole_batch else L.SETS_PER_SEQUENCE
         h = _take_over(self.eng, into, lambda out: self.eng.lib.bsk_result_sets_counted(self.eng.ctx, self.h, scope, scale, out))
+        if into is not None:
+            into.group_offsets = None
         return into if into is not None else Sets(self.eng, h)
+
+    def window_sets(self, window: int = 0, step: int = 0, count: int = 0, scale: int = 1, counted: bool = False, into: Optional["Sets"] = None) -> "Sets":
+        """One set per window of every sequence's positions, left on the device (bsk_result_sets_windows): windows of `window` positions
+        whose starts are `step` apart (0: no overlap), or -- count != 0 -- `count` windows per sequence, sized per sequence (kmcp's
+        --split-number).  The windows of a sequence follow from its tuples, not from its length.  counted: every value with its run
+        length inside the window.  into: a Sets of this engine to re-use.  The returned Sets carries .group_offsets, the host array
+        [n_reads + 1] with window w of sequence i at set group_offsets[i] + w: the offsets that Sets.reduce and Hits.fold take."""
+        self.eng._opts()
+        wp = L.WindowParams(window, step, count, L.WINDOWS_COUNTED if counted else 0)
+        go = np.zeros(self.info()["n_reads"] + 1, np.uint64)
+        h = _take_over(self.eng, into, lambda out: self.eng.lib.bsk_result_sets_windows(self.eng.ctx, self.h, C.byref(wp), scale, out, go.ctypes.data))
+        res = into if into is not None else Sets(self.eng, h)
+        res.group_offsets = go
+        return res
 
     def compact(self):
         """bsk_result_compact: dense CSR copy left ON THE DEVICE -> (offsets_ptr, hash_ptr, pos_ptr or None, n_tuples); the arrays belong
@@ -319,6 +335,7 @@ class Sets(_Owner):
     """Device-resident sorted distinct value sets (bsk_sets): offsets[n_sets+1] and values[] stay on the device until close()."""
 
     _release = "bsk_sets_release"
+    group_offsets = None  # BatchResult.window_sets: the sets' windows by sequence (host, [n_reads + 1]); None on sets from any other call
 
     def __init__(self, eng: "Engine", handle):
         self.eng, self.h = eng, handle
@@ -358,6 +375,8 @@ class Sets(_Owner):
     # -- set algebra (bsk_sets_op / bsk_sets_reduce): the result is a Sets of the same engine, left on the device
     def _into(self, into: Optional["Sets"], call) -> "Sets":
         h = _take_over(self.eng, into, call)
+        if into is not None:
+            into.group_offsets = None  # (after the call: a refused call leaves the object, and its windows, as they were)
         return into if into is not None else Sets(self.eng, h)
 
     def op(self, other: "Sets", op: int, into: Optional["Sets"] = None) -> "Sets":
@@ -696,6 +715,7 @@ class Hits(_Owner):
 
     _release = "bsk_hits_release"
     _totals = None  # total[] of hits with totals (Sets.neighbors), fetched with the others
+    _members = None  # members[] of folded hits (Hits.fold), fetched with the others
     _weights = _norms = _operands = None  # the weighted side (Sets.neighbors_counted): (dot, min_sum), fetched with the others; (sumsq_a, sumsq_b, totals_a, totals_b); (a, b, limit)
 
     def __init__(self, eng: "Engine"):
@@ -703,7 +723,7 @@ class Hits(_Owner):
         self._host = None
 
     def _bind(self, h, query_sizes: np.ndarray, target_sizes: np.ndarray, operands=None):
-        self.h, self._host, self._totals = h, None, None
+        self.h, self._host, self._totals, self._members = h, None, None, None
         self._weights, self._norms, self._operands = None, None, operands
         self.query_sizes, self.target_sizes = query_sizes.astype(np.uint64), target_sizes
 
@@ -725,6 +745,47 @@ class Hits(_Owner):
         res = reuse if reuse is not None else Hits(self.eng)
         res._bind(h, self.query_sizes, self.target_sizes)
         return res
+
+    def fold(self, group_offsets, min_members: int = 1, min_fraction=None, reuse: Optional["Hits"] = None) -> "Hits":
+        """The hits summed by target group (bsk_hits_fold) -> Hits whose targets are groups: group g is targets group_offsets[g] ..
+        group_offsets[g + 1] - 1 (the chunks of a genome: Sets.group_offsets of BatchResult.window_sets).  Per row and group with a hit:
+        shared summed (saturating), .members = how many of the group's targets the row hit.  A group is kept with at least min_members
+        members and, with min_fraction = (num, den), members * den >= num * group_size.  The rows must list their targets strictly
+        ascending (not the output of top()).  reuse: any Hits of this engine, but not self."""
+        go = np.ascontiguousarray(group_offsets, np.uint64)
+        if go.ndim != 1 or go.size == 0:
+            raise ValueError("group_offsets: a one-dimensional array of n_groups + 1 entries")
+        num, den = (0, 0) if min_fraction is None else (int(min_fraction[0]), int(min_fraction[1]))
+        fp = L.FoldParams(min_members, 0, num, den)
+        h = _take_over(self.eng, reuse, lambda out: self.eng.lib.bsk_hits_fold(self.eng.ctx, self.h, go.ctypes.data, go.size - 1, C.byref(fp), out))
+        res = reuse if reuse is not None else Hits(self.eng)
+        res._bind(h, self.query_sizes, np.diff(go))
+        return res
+
+    def has_members(self) -> bool:
+        """whether the last entry that wrote these hits kept members (bsk_hits_members_device gives an array): fold() does"""
+        if not self.h:
+            return self._members is not None
+        pm = C.c_void_p()
+        self.eng._chk(self.eng.lib.bsk_hits_members_device(self.h, C.byref(pm)))
+        return bool(pm.value)
+
+    def fetch_members(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """bsk_hits_fetch_members -> members[] of the hits of the range; hits without members raise"""
+        inf = self.info()
+        if count is None:
+            count = inf["n_queries"] - first
+        mm = np.zeros(max(inf["n_hits"], 1), np.uint32)
+        offs = np.zeros(count + 1, np.uint64)
+        self.eng._chk(self.eng.lib.bsk_hits_fetch(self.eng.ctx, self.h, first, count, offs.ctypes.data, None, None, 0))
+        self.eng._chk(self.eng.lib.bsk_hits_fetch_members(self.eng.ctx, self.h, first, count, mm.ctypes.data, mm.size))
+        return mm[:int(offs[-1])]
+
+    @property
+    def members(self) -> Optional[np.ndarray]:
+        """per hit of folded hits how many targets of its group the row hit; None for hits without members (anything but fold())"""
+        self._cache()
+        return self._members
 
     def cluster(self, method="components", score=None, reuse: Optional["Clusters"] = None) -> "Clusters":
         """The hits read as an undirected graph over their queries, clustered on the device (bsk_hits_cluster) -> Clusters.
@@ -808,6 +869,7 @@ class Hits(_Owner):
             self._host = self.fetch()
             self._totals = self.fetch_totals() if self.has_totals() else None
             self._weights = self.fetch_weights() if self.has_weights() else None
+            self._members = self.fetch_members() if self.has_members() else None
         return self._host
 
     @property

@@ -495,6 +495,10 @@ int bsk_result_sets(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk
  *     (BSK_ERR_UNSUPPORTED), BSK_ERR_NOMEM and BSK_ERR_DEVICE release.
  *   bsk_hits_cluster (bsk_clusters **out) and bsk_hits_from_host: every BSK_ERR_ARG and the 2^32 limits keep the slot; BSK_ERR_NOMEM and
  *     BSK_ERR_DEVICE release.
+ *   bsk_hits_fold: every BSK_ERR_ARG -- a row that is not strictly ascending and a target beyond the last group included, which one
+ *     small device pass finds before the object is taken over -- and the 2^32 limits keep the slot; BSK_ERR_NOMEM and BSK_ERR_DEVICE release.
+ *   bsk_result_sets_windows: as bsk_sets_compare -- every BSK_ERR_ARG keeps the slot; both 2^32 limits (BSK_ERR_UNSUPPORTED: the windows in
+ *     total, the gathered tuples), known after a read-back, release it, as BSK_ERR_NOMEM and BSK_ERR_DEVICE do.
  *   bsk_result_sets_reuse, _counted: a NULL `sets` and sets of another context (BSK_ERR_ARG) keep the slot.  Every other error releases:
  *     a NULL r, a bad scope, a bad scale and a result of another context (BSK_ERR_ARG all four), the 2^32 limit, memory, the device.
  * bsk_result_sets, bsk_sets_from_host and bsk_index_build only write their slot: it is NULL after an error, whatever it held
@@ -731,6 +735,79 @@ int bsk_compare_weights_device(const bsk_compare *c, const uint64_t **dot, const
 int bsk_compare_fetch_weights(bsk_ctx *ctx, const bsk_compare *c, uint64_t first_row, uint64_t n_rows,
                               uint64_t *dot, uint64_t *min_sum, uint64_t cell_cap);                       /* either array may be NULL */
 int bsk_sets_sumsq(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t count, uint64_t *sumsq /* host */);
+
+/* ---- window sets and folded hits: genome chunks as search targets ----
+ * kmcp indexes one k-mer set per CHUNK of a reference (--split-number, --split-size, --split-overlap) and counts how many chunks of a
+ * genome a read set hits (--min-chunks-fraction); fastANI and skani work on fragments in the same way.  Two entries serve that
+ * workflow on the device: genome -> window sets -> index; reads -> search -> hits folded per genome, with the chunks hit -> top.
+ *
+ * bsk_result_sets_windows: one set per window of a sequence.
+ *   Tuple j of a sequence has position p = pos[] & ~BSK_POS_STRAND_BIT.  For the every-position kinds, whose pos is NULL, p = j.
+ *   A sequence with c tuples has last position P.
+ *   In count mode (wp->count != 0), for that sequence, W = max(1, ceil((P + 1) / count)) and S = W.
+ *   In all other cases W = window and S = step ? step : window.
+ *   first(p) = p < W ? 0 : (p - W) / S + 1.  With S == W this is p / W.
+ *   The sequence has nwin = c ? first(P) + 1 : 0 windows.
+ *   Window w holds the tuples with w*S <= p < w*S + W.
+ *   Consequences: every tuple lies in at least one window; with S < W a tuple lies in several windows; interior windows without
+ *   tuples are empty sets; in count mode nwin <= count.
+ *   The window count is derived from the TUPLES, not from the sequence length: a result does not keep lengths.  A sequence whose
+ *   last bases select no tuple has fewer windows than its length would give, and a sequence without tuples has none.
+ *   Set number seq_offsets[i] + w is window w of sequence i, and seq_offsets[n_reads] equals the number of sets.  seq_offsets is a
+ *   host array of n_reads + 1 entries, or NULL.
+ *   Values are handled exactly as in bsk_result_sets: distinct and ascending, through the FracMinHash filter hash <= MaxUint64/scale;
+ *   with BSK_WINDOWS_COUNTED each value carries its run length inside the window (a counted bsk_sets).
+ *   The output is an ordinary bsk_sets: index, search, op, reduce, compare, neighbours and fetch all work unchanged.  By construction
+ *   bsk_sets_reduce(windows, seq_offsets, n_reads, 1) equals bsk_result_sets(r, BSK_SETS_PER_SEQUENCE, scale) value for value, for any step.
+ *   Errors.  BSK_ERR_ARG, which keeps the slot: a NULL ctx, r, wp or sets; both or neither of window and count set; step > window; step
+ *   set in count mode; window >= 2^31; an unknown flag bit; scale < 0; a result or *sets of another context.  BSK_ERR_UNSUPPORTED (2^32
+ *   or more windows in total, or 2^32 or more gathered tuples with the overlap multiplicity counted: both totals are known after a
+ *   read-back), BSK_ERR_NOMEM and BSK_ERR_DEVICE release the slot.
+ *   How it runs.  A sequence's tuples are stored in position order, so a window is a contiguous span (first tuple, count, stride) of
+ *   them, found by two searches over the sequence's positions (k_win_count, the library's scan, k_win_spans); the spans -- which may
+ *   overlap -- then go through the very path of bsk_result_sets: its small-set kernel, its segmented sort, its filter, its counts.
+ *
+ * bsk_hits_fold: hits by target group, with the members hit.
+ *   Group g is targets group_offsets[g] .. group_offsets[g + 1] - 1; group_offsets[0] == 0, non-decreasing, the last at most 2^32 and
+ *   n_groups < 2^32, else BSK_ERR_ARG (checked on the host).  Empty groups are legal.  The pointer is not retained.
+ *   The output has the rows of h.  Per row there is one hit for every group of which the row hit at least one target and which passes
+ *   both conditions of fp: target = g, ascending inside the row; shared = the sum of the members' shared, saturating at 2^32-1;
+ *   members = how many of the group's targets the row hit, a fifth u32 array parallel to target (bsk_hits_members_device,
+ *   bsk_hits_fetch_members).  A group is kept iff members >= max(min_members, 1) and, with frac_den != 0,
+ *   (uint64_t)members * frac_den >= (uint64_t)frac_num * group_size (exact: no rounding, no division).  fp == NULL is {1, 0, 0, 0}.
+ *   members follows the rule of total and the weights: every entry that writes hits without members into a re-used object leaves it
+ *   without members; the array is kept and only grows.  The output carries neither totals nor weights, whatever h carried.
+ *   bsk_hits_info / _fetch / _top / _cluster / _release work on it unchanged; the output of bsk_hits_top carries no members.
+ *   The input must have targets strictly ascending inside every row: search, neighbours and from-host results do, bsk_hits_top results
+ *   do not.  One small device pass (k_fold_check) finds a row that is not strictly ascending and a target >= group_offsets[n_groups]
+ *   before the object is taken over: both are BSK_ERR_ARG and keep the slot.  So do *out == h, a foreign context, a NULL argument, a
+ *   flag bit, frac_num > frac_den with frac_den != 0, and the 2^32 limits (rows, hits: BSK_ERR_UNSUPPORTED).  BSK_ERR_NOMEM and
+ *   BSK_ERR_DEVICE release the slot.  n_queries == 0 gives an empty result with BSK_OK.
+ *   How it runs: a u32 map target -> group (k_fold_map); a head where a row starts or the group changes (k_fold_check); the library's
+ *   scan; every head's owner walks its run and sums it (k_fold_runs); the kept runs are placed (k_fold_place).  No atomics on the
+ *   output and no kernel that waits on another: the result is bit-identical from call to call.  bsk_hits_plan names the kernels and
+ *   reports groups= and kept= as decimal figures; n_large_queries is 0.
+ *   bsk_hits_members_device: *members = NULL for hits without members.  bsk_hits_fetch_members: the members of the hits of rows first ..
+ *   first + count - 1, with the range, cap and foreign-context rules of bsk_hits_fetch_totals; BSK_ERR_ARG for hits without members. */
+enum { BSK_WINDOWS_COUNTED = 1 };
+typedef struct bsk_window_params {
+    uint32_t window;  /* positions per window; 0 iff count != 0 */
+    uint32_t step;    /* distance between window starts; 0 = window (no overlap); 1 <= step <= window */
+    uint32_t count;   /* != 0: `count` windows per sequence, sized per sequence (kmcp --split-number); window and step must be 0 */
+    uint32_t flags;   /* BSK_WINDOWS_COUNTED or 0; any other bit: BSK_ERR_ARG */
+} bsk_window_params;
+int bsk_result_sets_windows(bsk_ctx *ctx, const bsk_result *r, const bsk_window_params *wp, int scale,
+                            bsk_sets **sets, uint64_t *seq_offsets /* host, [n_reads + 1], or NULL */);
+typedef struct bsk_fold_params {
+    uint32_t min_members;  /* keep a group only if >= this many of its targets were hit; 0 is taken as 1 */
+    uint32_t flags;        /* 0; any bit: BSK_ERR_ARG */
+    uint32_t frac_num;     /* with frac_den != 0: keep iff members * frac_den >= frac_num * group_size (u64, exact) */
+    uint32_t frac_den;     /* 0: no such condition; frac_num > frac_den with frac_den != 0: BSK_ERR_ARG */
+} bsk_fold_params;
+int bsk_hits_fold(bsk_ctx *ctx, const bsk_hits *h, const uint64_t *group_offsets /* host, [n_groups + 1] */, uint64_t n_groups,
+                  const bsk_fold_params *fp /* NULL: {1,0,0,0} */, bsk_hits **out);
+int bsk_hits_members_device(const bsk_hits *h, const uint32_t **members);  /* NULL for hits without members */
+int bsk_hits_fetch_members(bsk_ctx *ctx, const bsk_hits *h, uint64_t first, uint64_t count, uint32_t *members, uint64_t hit_cap);
 
 /* ---- clusters of a neighbour graph: connected components and greedy representatives ----
  * (bsk_sets_neighbors, which makes such a graph from sets, is declared below this block: it closes the header.)
