@@ -1,7 +1,7 @@
 // compare.hip -- MinHash on the device: bottom-n sets (bsk_sets_bottom) and the dense all-pairs comparison (bsk_sets_compare), what
 // mash dist / triangle, sourmash compare, dereplication and clustering start from.
 //
-// k_cmp_tile.  A GEMM-shaped problem whose inner product is a merge of two sorted u64 lists.  A workgroup owns a tile of
+// The tile machine.  A GEMM-shaped problem whose inner product is a merge of two sorted u64 lists.  A workgroup owns a tile of
 // CMP_ROWS x CMP_COLS pairs, one lane per pair; the tile's CMP_ROWS + CMP_COLS sets pass through LDS once per tile, not once per pair.
 // The pairs advance through their sets at different rates, so the sets are staged BY VALUE RANGE, in rounds.  Every set of the tile
 // has an effective prefix of min(limit, size) values (no pair can walk past the limit-th value of either set) and a cursor.  A round:
@@ -19,28 +19,31 @@
 // -- different c, any j -- never meet on a bank, and the two rows of a half at most 2-way.  The staging thread (j, c) = (k * 16 + t / 16,
 // t % 16) writes s_b[k * 256 + t]: consecutive, conflict-free.
 //
-// k_cmp_tile_w (bsk_sets_compare_counted): the tile, round rule and window of k_cmp_tile, with a u32 count window beside every value
-// window -- s_ac[r * CMP_WINDOW + j] and s_bc[j * CMP_COLS + c], the indices of the values -- staged in the loops that stage the values,
-// from the cursors the values use, so a value that is copied again next round brings its count again.  A lane reads two counts only
-// where its two values are equal, at the indices they were read from, and keeps two more sums: the products (u64, saturating) and the
-// minima (u64, exact).  An uncounted operand's count window is filled with ones.  ds_read_b32 banks are (dword mod 32): the lanes of a
-// row read one a-count (broadcast) and the b-counts (j & 1) * 16 + c -- never two lanes of a row on one bank, the two rows of a
-// 32-lane half at most 2-way, as for the values.  k_cmp_tile itself is not touched.
+// All of this is ONE device body, cmp_tile<W, NB>, and three kernels are its instantiations: k_cmp_tile <false, false>
+// (bsk_sets_compare), k_cmp_tile_w <true, false> (bsk_sets_compare_counted) and k_cmp_tile_nb <false, true> (bsk_sets_neighbors).
+// What a flag does not select is not in the kernel: neither its code nor its LDS (33 544 / 49 928 / 33 568 bytes a workgroup, in that
+// order).  The fourth, k_cmp_tile_nb_w (bsk_sets_neighbors_counted; 49 952 bytes), does both things and is still a copy of the
+// machine: instantiated from the body it measured 3.3 % slower, so a change to the machine is made twice, not once.
 //
-// k_cmp_tile_nb (bsk_sets_neighbors): the tile, rounds and LDS plan of k_cmp_tile, and another end.  No cell is stored: every lane applies
-// the caller's rule (shared count, exact Jaccard fraction, j > i) to its pair; the four ballots of the workgroup give the tile's kept
-// pairs and the kept pairs of each of its rows; the tile reserves its records with ONE atomic on a global cursor, adds its rows' counts to
-// row_count[] (only rows that keep something) and every keeping lane stores one 16-byte record (row, column, shared, total).  The cursor
-// counts every kept pair whether or not its record fits, so when the room is too small the host knows the exact need and runs the kernel
-// once more.  With BSK_NEIGHBORS_UPPER a tile whose every pair has j <= i is not run at all.  The records arrive in the order the tiles
-// finish; the order of the RESULT does not depend on it: the scan of row_count[] places the rows, a record takes any free place of its
-// row as the key (column << 32) | record, the library's segmented key sort orders every row by column (the columns of a row are
-// distinct: the record half of a key never decides), and a gather writes target, shared and total.  k_cmp_tile itself is not touched.
+// W adds the counts: a u32 count window beside every value window -- s_ac[r * CMP_WINDOW + j] and s_bc[j * CMP_COLS + c], the indices
+// of the values -- staged in the loops that stage the values, from the cursors the values use, so a value that is copied again next
+// round brings its count again.  A lane reads two counts only where its two values are equal, at the indices they were read from, and
+// keeps two more sums: the products (u64, saturating) and the minima (u64, exact).  An uncounted operand's count window is filled with
+// ones.  ds_read_b32 banks are (dword mod 32): the lanes of a row read one a-count (broadcast) and the b-counts (j & 1) * 16 + c --
+// never two lanes of a row on one bank, the two rows of a 32-lane half at most 2-way, as for the values.  The count windows are 16 KB:
+// three workgroups a CU (CMP_W_BLOCKS_PER_CU), not four.
 //
-// k_cmp_tile_nb_w (bsk_sets_neighbors_counted): the rounds, count windows and merge loop of k_cmp_tile_w and the epilogue of k_cmp_tile_nb.
-// The rule reads shared and total only, so the kept pairs and their order are those of k_cmp_tile_nb; a keeping lane stores the same
-// 16-byte record and, at the same slot of a second array, 16 bytes of (dot, min_sum).  k_nb_keys and the key sort run as they are; the
-// gather (k_nb_place_w) reads both arrays by the sorted keys.
+// NB replaces the end.  No cell is stored: every lane applies the caller's rule (shared count, exact Jaccard fraction, j > i) to its
+// pair -- the rule reads shared and total only, never the weights, so the kept pairs are the same with and without W; the four ballots of
+// the workgroup give the tile's kept pairs and the kept pairs of each of its rows; the tile reserves its records with ONE atomic on a
+// global cursor, adds its rows' counts to row_count[] (only rows that keep something) and every keeping lane stores one 16-byte record
+// (row, column, shared, total) and, in k_cmp_tile_nb_w, 16 bytes of (dot, min_sum) at the same slot of a second array.  The cursor counts every
+// kept pair whether or not its record fits, so when the room is too small the host knows the exact need and runs the kernel once more.
+// With BSK_NEIGHBORS_UPPER a tile whose every pair has j <= i is not run at all.  The records arrive in the order the tiles finish; the
+// order of the RESULT does not depend on it: the scan of row_count[] places the rows, a record takes any free place of its row as the
+// key (column << 32) | record (k_nb_keys), the library's segmented key sort orders every row by column (the columns of a row are
+// distinct: the record half of a key never decides), and a gather by the sorted keys writes target, shared and total (k_nb_place) and
+// the weights too (k_nb_place_w).
 //
 // bsk_sets_bottom: the sizes min(n, size) through the library's scan, then a gather by groups of lanes (8 per set while the kept sets
 // average at most CMP_BT_SMALL values, else a wavefront per set).
@@ -82,17 +85,54 @@ namespace {
 static_assert(CMP_THREADS == 256 && CMP_THREADS / CMP_COLS == CMP_ROWS && CMP_SETS <= 64, "one lane per pair; the first wavefront keeps the sets' cursors");
 static_assert(CMP_WINDOW % CMP_ROWS == 0 && (CMP_ROWS * CMP_WINDOW) % CMP_THREADS == 0, "the staging loops have no tail");
 
-__global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile(const u64 *aoff, const u64 *av, u64 n_a, const u64 *boff, const u64 *bv, u64 n_b, u32 lim, u64 ntiles,
-                                                         u64 tiles_x, u32 *shared, u32 *total, u64 *fig) {
+// where a tile's results go: the cells of the dense end (dot / msum with counts only) ...
+struct TileCells {
+    u32 *shared, *total;
+    u64 *dot, *msum;
+};
+// ... or the rule and the records of the sparse end
+struct NbRule {
+    u32 min_shared, num, den, upper;  // den == 0: no Jaccard condition; upper != 0: only pairs with j > i
+};
+struct TileRecords {
+    NbRule rule;
+    u64 room;  // records that rec can hold
+    uint4 *rec;
+    u32 *row_count;
+};
+
+// LDS of a workgroup without counts: the value windows and cursors, and the sparse end's words, four workgroups a CU (CMP_BLOCKS_PER_CU)
+// within 160 KiB; with counts (12 bytes a value) three: the statement beside k_cmp_tile_nb_w below covers k_cmp_tile_w, which has no such words
+static_assert((CMP_SETS * CMP_WINDOW) * 8 + CMP_SETS * (8 + 4 + 4) + 4 + (CMP_THREADS / 64) * 4 + 8 <= 160 * 1024 / CMP_BLOCKS_PER_CU,
+              "k_cmp_tile_nb: 33 308 bytes of LDS a workgroup, 40 960 available");
+
+// the tile machine of k_cmp_tile, k_cmp_tile_w and k_cmp_tile_nb (k_cmp_tile_nb_w keeps a copy: see there).  W: counts beside the values (ac / bc NULL: an uncounted operand, every count 1).  NB: the sparse
+// end -- the rule per lane and a record per kept pair -- in place of the cell store.  What an instantiation does not use (ac / bc, one of
+// cells / recs, the LDS objects of the other forms) is touched under `if constexpr` only and is not in its code.
+template <bool W, bool NB>
+__device__ __forceinline__ void cmp_tile(const u64 *aoff, const u64 *av, const u32 *ac, u64 n_a, const u64 *boff, const u64 *bv, const u32 *bc, u64 n_b, u32 lim, u64 ntiles,
+                                         u64 tiles_x, const TileCells &cells, const TileRecords &recs, u64 *fig) {
     __shared__ u64 s_a[CMP_ROWS * CMP_WINDOW];
     __shared__ u64 s_b[CMP_COLS * CMP_WINDOW];
-    __shared__ u64 s_from[CMP_SETS];  // the set's first unstaged value (index into av / bv)
-    __shared__ u32 s_n[CMP_SETS];     // values copied to its window this round
-    __shared__ u32 s_cnt[CMP_SETS];   // ... and how many of them lie below v_hi: the window's end
+    __shared__ u32 s_ac[CMP_ROWS * CMP_WINDOW];  // W: the count of s_a[i]
+    __shared__ u32 s_bc[CMP_COLS * CMP_WINDOW];  // W: the count of s_b[i]
+    __shared__ u64 s_from[CMP_SETS];             // the set's first unstaged value (index into av / bv)
+    __shared__ u32 s_n[CMP_SETS];                // values copied to its window this round
+    __shared__ u32 s_cnt[CMP_SETS];              // ... and how many of them lie below v_hi: the window's end
     __shared__ int s_last;
+    __shared__ u32 s_wk[CMP_THREADS / 64];  // NB: kept pairs of every wavefront of the tile
+    __shared__ u64 s_base;                  // NB: the tile's first record
+    static_assert(!(W && NB), "both at once is k_cmp_tile_nb_w's own copy");
     const int t = threadIdx.x, r = t / CMP_COLS, c = t % CMP_COLS;
+    u32 skipped = 0;
     for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const u64 i0 = (tile / tiles_x) * CMP_ROWS, j0 = (tile % tiles_x) * CMP_COLS;
+        if constexpr (NB) {
+            if (recs.rule.upper && j0 + CMP_COLS <= i0 + 1) {  // every pair of the tile has j <= i (equal tile sides: tile column < tile row)
+                ++skipped;
+                continue;
+            }
+        }
         // threads 0 .. CMP_SETS - 1 keep a set each: rows first, then columns
         const u64 *vals = t < CMP_ROWS ? av : bv;
         u64 base = 0;
@@ -109,6 +149,7 @@ __global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile(const u64 *aoff, const
         }
         const bool pair = i0 + r < n_a && j0 + c < n_b;
         u32 tot = 0, sh = 0, rounds = 0;
+        u64 dt = 0, ms = 0;
         for (;;) {
             u64 cand = 0;
             bool has = false;
@@ -124,12 +165,18 @@ __global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile(const u64 *aoff, const
 #pragma unroll
             for (int k = 0; k < CMP_ROWS * CMP_WINDOW / CMP_THREADS; ++k) {
                 const int idx = k * CMP_THREADS + t, s = idx / CMP_WINDOW, j = idx % CMP_WINDOW;
-                if ((u32)j < s_n[s]) s_a[idx] = av[s_from[s] + j];
+                if ((u32)j < s_n[s]) {
+                    s_a[idx] = av[s_from[s] + j];
+                    if constexpr (W) s_ac[idx] = ac ? ac[s_from[s] + j] : 1u;
+                }
             }
 #pragma unroll
             for (int k = 0; k < CMP_WINDOW / CMP_ROWS; ++k) {
                 const int j = k * CMP_ROWS + r;
-                if ((u32)j < s_n[CMP_ROWS + c]) s_b[k * CMP_THREADS + t] = bv[s_from[CMP_ROWS + c] + j];
+                if ((u32)j < s_n[CMP_ROWS + c]) {
+                    s_b[k * CMP_THREADS + t] = bv[s_from[CMP_ROWS + c] + j];
+                    if constexpr (W) s_bc[k * CMP_THREADS + t] = bc ? bc[s_from[CMP_ROWS + c] + j] : 1u;
+                }
             }
             __syncthreads();
             if (t < 64) {  // the first wavefront: v_hi, the windows' ends, the cursors
@@ -166,133 +213,17 @@ __global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile(const u64 *aoff, const
                     for (;;) {
                         ++tot;
                         const bool le = x <= y, ge = x >= y;
-                        sh += (le && ge) ? 1u : 0u;
-                        ia += le ? 1u : 0u;
-                        ib += ge ? 1u : 0u;
-                        if (tot >= lim || ia >= ea || ib >= eb) break;
-                        if (le) x = s_a[r * CMP_WINDOW + ia];
-                        if (ge) y = s_b[ib * CMP_COLS + c];
-                    }
-                }
-                // one window is exhausted: what the other still holds lies inside the round's range and is not in the first
-                const u32 rest = (ea - ia) + (eb - ib), room = lim - tot;
-                tot += rest < room ? rest : room;
-            }
-            const int last = s_last;
-            if (!__syncthreads_or(pair && tot < lim) || last) break;
-        }
-        if (pair) {
-            const u64 cell = (i0 + r) * n_b + j0 + c;
-            shared[cell] = sh;
-            total[cell] = tot;
-        }
-        if (t == 0) {
-            atomicAdd((unsigned long long *)&fig[0], 1ull);
-            atomicAdd((unsigned long long *)&fig[1], (unsigned long long)rounds);
-            atomicMax((unsigned long long *)&fig[2], (unsigned long long)rounds);
-        }
-    }
-}
-
-// the weighted tile: k_cmp_tile's rounds, with the counts beside the values (ac / bc NULL: an uncounted operand, every count 1)
-__global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile_w(const u64 *aoff, const u64 *av, const u32 *ac, u64 n_a, const u64 *boff, const u64 *bv, const u32 *bc, u64 n_b,
-                                                           u32 lim, u64 ntiles, u64 tiles_x, u32 *shared, u32 *total, u64 *dot, u64 *msum, u64 *fig) {
-    __shared__ u64 s_a[CMP_ROWS * CMP_WINDOW];
-    __shared__ u64 s_b[CMP_COLS * CMP_WINDOW];
-    __shared__ u32 s_ac[CMP_ROWS * CMP_WINDOW];  // the count of s_a[i]
-    __shared__ u32 s_bc[CMP_COLS * CMP_WINDOW];  // the count of s_b[i]
-    __shared__ u64 s_from[CMP_SETS];
-    __shared__ u32 s_n[CMP_SETS];
-    __shared__ u32 s_cnt[CMP_SETS];
-    __shared__ int s_last;
-    const int t = threadIdx.x, r = t / CMP_COLS, c = t % CMP_COLS;
-    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const u64 i0 = (tile / tiles_x) * CMP_ROWS, j0 = (tile % tiles_x) * CMP_COLS;
-        const u64 *vals = t < CMP_ROWS ? av : bv;
-        u64 base = 0;
-        u32 len = 0, start = 0;
-        if (t < CMP_SETS) {
-            const bool isa = t < CMP_ROWS;
-            const u64 g = isa ? i0 + t : j0 + (t - CMP_ROWS);
-            const u64 *off = isa ? aoff : boff;
-            if (g < (isa ? n_a : n_b)) {
-                base = off[g];
-                const u64 sz = off[g + 1] - base;
-                len = sz < (u64)lim ? (u32)sz : lim;
-            }
-        }
-        const bool pair = i0 + r < n_a && j0 + c < n_b;
-        u32 tot = 0, sh = 0, rounds = 0;
-        u64 dt = 0, ms = 0;
-        for (;;) {
-            u64 cand = 0;
-            bool has = false;
-            if (t < CMP_SETS) {
-                const u32 rem = len - start;
-                has = rem > CMP_WINDOW;
-                s_from[t] = base + start;
-                s_n[t] = has ? CMP_WINDOW : rem;
-                if (has) cand = vals[base + start + CMP_WINDOW];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < CMP_ROWS * CMP_WINDOW / CMP_THREADS; ++k) {
-                const int idx = k * CMP_THREADS + t, s = idx / CMP_WINDOW, j = idx % CMP_WINDOW;
-                if ((u32)j < s_n[s]) {
-                    s_a[idx] = av[s_from[s] + j];
-                    s_ac[idx] = ac ? ac[s_from[s] + j] : 1u;
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < CMP_WINDOW / CMP_ROWS; ++k) {
-                const int j = k * CMP_ROWS + r;
-                if ((u32)j < s_n[CMP_ROWS + c]) {
-                    s_b[k * CMP_THREADS + t] = bv[s_from[CMP_ROWS + c] + j];
-                    s_bc[k * CMP_THREADS + t] = bc ? bc[s_from[CMP_ROWS + c] + j] : 1u;
-                }
-            }
-            __syncthreads();
-            if (t < 64) {
-                const bool any = __ballot(has) != 0;
-                u64 vhi = has ? cand : ~0ull;
-                for (int d = 32; d; d >>= 1) {
-                    const u64 o = __shfl_xor(vhi, d, 64);
-                    vhi = o < vhi ? o : vhi;
-                }
-                if (t < CMP_SETS) {
-                    u32 cnt = s_n[t];
-                    if (any) {
-                        u32 lo = 0, hi = cnt;
-                        while (lo < hi) {
-                            const u32 mid = (lo + hi) >> 1;
-                            const u64 v = t < CMP_ROWS ? s_a[t * CMP_WINDOW + mid] : s_b[mid * CMP_COLS + (t - CMP_ROWS)];
-                            if (v < vhi) lo = mid + 1;
-                            else hi = mid;
-                        }
-                        cnt = lo;
-                    }
-                    s_cnt[t] = cnt;
-                    start += cnt;
-                }
-                if (t == 0) s_last = any ? 0 : 1;
-            }
-            __syncthreads();
-            ++rounds;
-            if (pair && tot < lim) {
-                const u32 ea = s_cnt[r], eb = s_cnt[CMP_ROWS + c];
-                u32 ia = 0, ib = 0;
-                if (ea && eb) {
-                    u64 x = s_a[r * CMP_WINDOW], y = s_b[c];
-                    for (;;) {
-                        ++tot;
-                        const bool le = x <= y, ge = x >= y;
-                        if (le && ge) {  // both hold it: its counts, from where the two values were read
-                            const u32 ca = s_ac[r * CMP_WINDOW + ia], cb = s_bc[ib * CMP_COLS + c];
-                            const u64 p = (u64)ca * cb;
-                            ++sh;
-                            dt += p;
-                            dt = dt < p ? ~0ull : dt;  // saturating: a wrapped sum is below its last term
-                            ms += ca < cb ? ca : cb;
+                        if constexpr (W) {
+                            if (le && ge) {  // both hold it: its counts, from where the two values were read
+                                const u32 ca = s_ac[r * CMP_WINDOW + ia], cb = s_bc[ib * CMP_COLS + c];
+                                const u64 p = (u64)ca * cb;
+                                ++sh;
+                                dt += p;
+                                dt = dt < p ? ~0ull : dt;  // saturating: a wrapped sum is below its last term
+                                ms += ca < cb ? ca : cb;
+                            }
+                        } else {
+                            sh += (le && ge) ? 1u : 0u;
                         }
                         ia += le ? 1u : 0u;
                         ib += ge ? 1u : 0u;
@@ -301,157 +232,48 @@ __global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile_w(const u64 *aoff, con
                         if (ge) y = s_b[ib * CMP_COLS + c];
                     }
                 }
-                // what the other window still holds is in one set only: it adds to the total, to neither sum
-                const u32 rest = (ea - ia) + (eb - ib), room = lim - tot;
-                tot += rest < room ? rest : room;
-            }
-            const int last = s_last;
-            if (!__syncthreads_or(pair && tot < lim) || last) break;
-        }
-        if (pair) {
-            const u64 cell = (i0 + r) * n_b + j0 + c;
-            shared[cell] = sh;
-            total[cell] = tot;
-            dot[cell] = dt;
-            msum[cell] = ms;
-        }
-        if (t == 0) {
-            atomicAdd((unsigned long long *)&fig[0], 1ull);
-            atomicAdd((unsigned long long *)&fig[1], (unsigned long long)rounds);
-            atomicMax((unsigned long long *)&fig[2], (unsigned long long)rounds);
-        }
-    }
-}
-
-// the sparse tile (bsk_sets_neighbors): k_cmp_tile's rounds, then the rule per lane and a record per kept pair -- no cell is stored
-struct NbRule {
-    u32 min_shared, num, den, upper;  // den == 0: no Jaccard condition; upper != 0: only pairs with j > i
-};
-__global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile_nb(const u64 *aoff, const u64 *av, u64 n_a, const u64 *boff, const u64 *bv, u64 n_b, u32 lim, u64 ntiles,
-                                                            u64 tiles_x, NbRule rule, u64 room, uint4 *rec, u32 *row_count, u64 *fig) {
-    __shared__ u64 s_a[CMP_ROWS * CMP_WINDOW];
-    __shared__ u64 s_b[CMP_COLS * CMP_WINDOW];
-    __shared__ u64 s_from[CMP_SETS];
-    __shared__ u32 s_n[CMP_SETS];
-    __shared__ u32 s_cnt[CMP_SETS];
-    __shared__ int s_last;
-    __shared__ u32 s_wk[CMP_THREADS / 64];  // kept pairs of every wavefront of the tile
-    __shared__ u64 s_base;                  // the tile's first record
-    const int t = threadIdx.x, r = t / CMP_COLS, c = t % CMP_COLS;
-    u32 skipped = 0;
-    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const u64 i0 = (tile / tiles_x) * CMP_ROWS, j0 = (tile % tiles_x) * CMP_COLS;
-        if (rule.upper && j0 + CMP_COLS <= i0 + 1) {  // every pair of the tile has j <= i (equal tile sides: tile column < tile row)
-            ++skipped;
-            continue;
-        }
-        const u64 *vals = t < CMP_ROWS ? av : bv;
-        u64 base = 0;
-        u32 len = 0, start = 0;
-        if (t < CMP_SETS) {
-            const bool isa = t < CMP_ROWS;
-            const u64 g = isa ? i0 + t : j0 + (t - CMP_ROWS);
-            const u64 *off = isa ? aoff : boff;
-            if (g < (isa ? n_a : n_b)) {
-                base = off[g];
-                const u64 sz = off[g + 1] - base;
-                len = sz < (u64)lim ? (u32)sz : lim;
-            }
-        }
-        const bool pair = i0 + r < n_a && j0 + c < n_b;
-        u32 tot = 0, sh = 0, rounds = 0;
-        for (;;) {
-            u64 cand = 0;
-            bool has = false;
-            if (t < CMP_SETS) {
-                const u32 rem = len - start;
-                has = rem > CMP_WINDOW;
-                s_from[t] = base + start;
-                s_n[t] = has ? CMP_WINDOW : rem;
-                if (has) cand = vals[base + start + CMP_WINDOW];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < CMP_ROWS * CMP_WINDOW / CMP_THREADS; ++k) {
-                const int idx = k * CMP_THREADS + t, s = idx / CMP_WINDOW, j = idx % CMP_WINDOW;
-                if ((u32)j < s_n[s]) s_a[idx] = av[s_from[s] + j];
-            }
-#pragma unroll
-            for (int k = 0; k < CMP_WINDOW / CMP_ROWS; ++k) {
-                const int j = k * CMP_ROWS + r;
-                if ((u32)j < s_n[CMP_ROWS + c]) s_b[k * CMP_THREADS + t] = bv[s_from[CMP_ROWS + c] + j];
-            }
-            __syncthreads();
-            if (t < 64) {
-                const bool any = __ballot(has) != 0;
-                u64 vhi = has ? cand : ~0ull;
-                for (int d = 32; d; d >>= 1) {
-                    const u64 o = __shfl_xor(vhi, d, 64);
-                    vhi = o < vhi ? o : vhi;
-                }
-                if (t < CMP_SETS) {
-                    u32 cnt = s_n[t];
-                    if (any) {
-                        u32 lo = 0, hi = cnt;
-                        while (lo < hi) {
-                            const u32 mid = (lo + hi) >> 1;
-                            const u64 v = t < CMP_ROWS ? s_a[t * CMP_WINDOW + mid] : s_b[mid * CMP_COLS + (t - CMP_ROWS)];
-                            if (v < vhi) lo = mid + 1;
-                            else hi = mid;
-                        }
-                        cnt = lo;
-                    }
-                    s_cnt[t] = cnt;
-                    start += cnt;
-                }
-                if (t == 0) s_last = any ? 0 : 1;
-            }
-            __syncthreads();
-            ++rounds;
-            if (pair && tot < lim) {
-                const u32 ea = s_cnt[r], eb = s_cnt[CMP_ROWS + c];
-                u32 ia = 0, ib = 0;
-                if (ea && eb) {
-                    u64 x = s_a[r * CMP_WINDOW], y = s_b[c];
-                    for (;;) {
-                        ++tot;
-                        const bool le = x <= y, ge = x >= y;
-                        sh += (le && ge) ? 1u : 0u;
-                        ia += le ? 1u : 0u;
-                        ib += ge ? 1u : 0u;
-                        if (tot >= lim || ia >= ea || ib >= eb) break;
-                        if (le) x = s_a[r * CMP_WINDOW + ia];
-                        if (ge) y = s_b[ib * CMP_COLS + c];
-                    }
-                }
+                // one window is exhausted: what the other still holds lies inside the round's range and is not in the first -- it adds to
+                // the total, to no other sum
                 const u32 rest = (ea - ia) + (eb - ib), left = lim - tot;
                 tot += rest < left ? rest : left;
             }
             const int last = s_last;
             if (!__syncthreads_or(pair && tot < lim) || last) break;
         }
-        // the epilogue: the rule per lane, the wavefronts' ballots, one reservation per tile.  A wavefront holds four rows of the tile, 16
-        // lanes each; the kept pairs are counted whether or not their records fit (the host grows the room and runs once more).
-        const u64 gi = i0 + r, gj = j0 + c;
-        const bool keep = pair && sh >= rule.min_shared && (rule.den == 0 || (u64)sh * rule.den >= (u64)rule.num * tot) && (!rule.upper || gj > gi);
-        const u64 m = __ballot(keep);
-        const int lane = t & 63, w = t >> 6;
-        if (lane == 0) s_wk[w] = (u32)__builtin_popcountll(m);
-        __syncthreads();
-        u32 before = 0, tile_kept = 0;
-#pragma unroll
-        for (int q = 0; q < CMP_THREADS / 64; ++q) {
-            before += q < w ? s_wk[q] : 0u;
-            tile_kept += s_wk[q];
-        }
-        if (tile_kept) {  // (the same for every thread of the workgroup)
-            if (t == 0) s_base = atomicAdd((unsigned long long *)&fig[3], (unsigned long long)tile_kept);
+        if constexpr (NB) {
+            // the epilogue: the rule per lane, the wavefronts' ballots, one reservation per tile.  A
+            // wavefront holds four rows of the tile, 16 lanes each; the kept pairs are counted whether or not their records fit (the host
+            // grows the room and runs once more).
+            const NbRule rule = recs.rule;
+            const u64 gi = i0 + r, gj = j0 + c;
+            const bool keep = pair && sh >= rule.min_shared && (rule.den == 0 || (u64)sh * rule.den >= (u64)rule.num * tot) && (!rule.upper || gj > gi);
+            const u64 m = __ballot(keep);
+            const int lane = t & 63, w = t >> 6;
+            if (lane == 0) s_wk[w] = (u32)__builtin_popcountll(m);
             __syncthreads();
-            const u64 slot = s_base + before + (u32)__builtin_popcountll(m & ((1ull << lane) - 1));
-            if (keep && slot < room) rec[slot] = make_uint4((u32)gi, (u32)gj, sh, tot);
-            if (c == 0) {  // the row's first lane: its 16 bits of the ballot
-                const u32 in_row = (u32)__builtin_popcountll((m >> (lane & 48)) & 0xffffull);
-                if (in_row) atomicAdd(&row_count[gi], in_row);
+            u32 before = 0, tile_kept = 0;
+#pragma unroll
+            for (int q = 0; q < CMP_THREADS / 64; ++q) {
+                before += q < w ? s_wk[q] : 0u;
+                tile_kept += s_wk[q];
+            }
+            if (tile_kept) {  // (the same for every thread of the workgroup)
+                if (t == 0) s_base = atomicAdd((unsigned long long *)&fig[3], (unsigned long long)tile_kept);
+                __syncthreads();
+                const u64 slot = s_base + before + (u32)__builtin_popcountll(m & ((1ull << lane) - 1));
+                if (keep && slot < recs.room) recs.rec[slot] = make_uint4((u32)gi, (u32)gj, sh, tot);
+                if (c == 0) {  // the row's first lane: its 16 bits of the ballot
+                    const u32 in_row = (u32)__builtin_popcountll((m >> (lane & 48)) & 0xffffull);
+                    if (in_row) atomicAdd(&recs.row_count[gi], in_row);
+                }
+            }
+        } else if (pair) {
+            const u64 cell = (i0 + r) * n_b + j0 + c;
+            cells.shared[cell] = sh;
+            cells.total[cell] = tot;
+            if constexpr (W) {
+                cells.dot[cell] = dt;
+                cells.msum[cell] = ms;
             }
         }
         if (t == 0) {
@@ -460,9 +282,28 @@ __global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile_nb(const u64 *aoff, co
             atomicMax((unsigned long long *)&fig[2], (unsigned long long)rounds);
         }
     }
-    if (t == 0 && skipped) atomicAdd((unsigned long long *)&fig[4], (unsigned long long)skipped);
+    if constexpr (NB) {
+        if (t == 0 && skipped) atomicAdd((unsigned long long *)&fig[4], (unsigned long long)skipped);
+    }
 }
 
+// the three instantiations: dense (bsk_sets_compare), dense with counts (bsk_sets_compare_counted), sparse (bsk_sets_neighbors)
+__global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile(const u64 *aoff, const u64 *av, u64 n_a, const u64 *boff, const u64 *bv, u64 n_b, u32 lim, u64 ntiles,
+                                                         u64 tiles_x, u32 *shared, u32 *total, u64 *fig) {
+    cmp_tile<false, false>(aoff, av, nullptr, n_a, boff, bv, nullptr, n_b, lim, ntiles, tiles_x, TileCells{shared, total, nullptr, nullptr}, TileRecords{}, fig);
+}
+__global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile_w(const u64 *aoff, const u64 *av, const u32 *ac, u64 n_a, const u64 *boff, const u64 *bv, const u32 *bc, u64 n_b,
+                                                           u32 lim, u64 ntiles, u64 tiles_x, u32 *shared, u32 *total, u64 *dot, u64 *msum, u64 *fig) {
+    cmp_tile<true, false>(aoff, av, ac, n_a, boff, bv, bc, n_b, lim, ntiles, tiles_x, TileCells{shared, total, dot, msum}, TileRecords{}, fig);
+}
+__global__ __launch_bounds__(CMP_THREADS) void k_cmp_tile_nb(const u64 *aoff, const u64 *av, u64 n_a, const u64 *boff, const u64 *bv, u64 n_b, u32 lim, u64 ntiles,
+                                                            u64 tiles_x, NbRule rule, u64 room, uint4 *rec, u32 *row_count, u64 *fig) {
+    cmp_tile<false, true>(aoff, av, nullptr, n_a, boff, bv, nullptr, n_b, lim, ntiles, tiles_x, TileCells{}, TileRecords{rule, room, rec, row_count}, fig);
+}
+
+// NOT an instantiation of the body: as cmp_tile<true, true> this kernel measured 3.3 % slower (same registers and LDS, the
+// same instructions scheduled otherwise), so it keeps its own copy of the tile machine.  A change to the rounds, the staging, the cursor
+// wavefront or the merge loop of cmp_tile is made here too.
 // the weighted sparse tile (bsk_sets_neighbors_counted): k_cmp_tile_w's rounds and count windows, k_cmp_tile_nb's epilogue.  The rule reads
 // shared and total only -- the weights are a payload -- so the kept pairs, their slots and row_count[] are those of k_cmp_tile_nb; a keeping
 // lane stores its record and, at the same slot of a second array, (dot, min_sum): two 16-byte stores.
