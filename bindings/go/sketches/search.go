@@ -100,6 +100,53 @@ func (ix *Index) Search(q *Sets, p SearchParams, into *Hits) (*Hits, error) {
 	return into, ix.eng.err(rc)
 }
 
+// BuildIndexCounted indexes the sets with their counts (bsk_index_build_counted): BuildIndex plus, per posting, the target's count
+// of the value, and per target the squared norm and the total of its counts.  Sets without counts give an index without counts.
+func (s *Sets) BuildIndexCounted() (*Index, error) {
+	ix := &Index{eng: s.eng}
+	rc := C.bsk_index_build_counted(s.eng.ctx, s.h, &ix.h)
+	runtime.KeepAlive(s)
+	if err := s.eng.err(rc); err != nil {
+		return nil, err
+	}
+	runtime.SetFinalizer(ix, func(ix *Index) { C.bsk_index_release(ix.h) })
+	return ix, nil
+}
+
+// Counted reports whether the index keeps counts (bsk_index_counted).
+func (ix *Index) Counted() bool {
+	var k C.int
+	C.bsk_index_counted(ix.h, &k)
+	runtime.KeepAlive(ix)
+	return k != 0
+}
+
+// Norms of targets [first, first+count): the sum of the squared counts (saturating at 2^64-1) and the sum of the counts
+// (bsk_index_fetch_norms); an index without counts reports the targets' sizes for both.
+func (ix *Index) Norms(first, count uint64) (sumsq, totals []uint64, err error) {
+	sumsq = make([]uint64, count+1)
+	totals = make([]uint64, count+1)
+	rc := C.bsk_index_fetch_norms(ix.eng.ctx, ix.h, C.uint64_t(first), C.uint64_t(count), (*C.uint64_t)(unsafe.Pointer(&sumsq[0])),
+		(*C.uint64_t)(unsafe.Pointer(&totals[0])))
+	runtime.KeepAlive(ix)
+	return sumsq[:count], totals[:count], ix.eng.err(rc)
+}
+
+// SearchCounted is Search with the counts (bsk_index_search_counted): the same hits, bit for bit -- the thresholds read the
+// shared count only -- and per hit the dot product and the sum of minima of the two count vectors over the shared values
+// ((*Hits).Weights, FetchWeights).  Queries or an index without counts count 1 for every value.  into: nil, or any Hits of this engine.
+func (ix *Index) SearchCounted(q *Sets, p SearchParams, into *Hits) (*Hits, error) {
+	if into == nil {
+		into = &Hits{eng: ix.eng}
+		runtime.SetFinalizer(into, func(h *Hits) { C.bsk_hits_release(h.h) })
+	}
+	sp := C.bsk_search_params{min_shared: C.uint32_t(p.MinShared), min_query_cov: C.double(p.MinQueryCov), min_target_cov: C.double(p.MinTargetCov)}
+	rc := C.bsk_index_search_counted(ix.eng.ctx, ix.h, q.h, &sp, &into.h)
+	runtime.KeepAlive(ix)
+	runtime.KeepAlive(q)
+	return into, ix.eng.err(rc)
+}
+
 // Info: queries and hits (bsk_hits_info).
 func (h *Hits) Info() (queries, hits uint64) {
 	var nq, nh C.uint64_t

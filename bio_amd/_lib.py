@@ -227,6 +227,10 @@ SYMBOLS = [
     ("bsk_hits_fold", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(FoldParams), _pp]),
     ("bsk_hits_members_device", C.c_int, [_vp, _pp]),
     ("bsk_hits_fetch_members", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64]),
+    ("bsk_index_build_counted", C.c_int, [_vp, _vp, _pp]),
+    ("bsk_index_counted", C.c_int, [_vp, C.POINTER(C.c_int)]),
+    ("bsk_index_fetch_norms", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
+    ("bsk_index_search_counted", C.c_int, [_vp, _vp, _vp, C.POINTER(SearchParams), _pp]),
 ]
 WINDOWS_COUNTED = 1
 NEIGHBORS_UPPER = 1

@@ -209,6 +209,39 @@ hipError_t sets_run_counts(hipStream_t st, const u64 *v, const u32 *keep, const 
     return hipGetLastError();
 }
 
+// The norms of sets first .. first + count - 1 (count != 0, the range checked by the caller) into a device array, on the context's stream
+// and without a synchronisation: what bsk_sets_totals and bsk_sets_sumsq copy to the host, and what a counted index keeps (search.hip).
+int sets_totals_device(bsk_ctx *ctx, const bsk_sets *s, u64 first, u64 count, u64 *out) {
+    hipStream_t st = ctx->stream;
+    const u64 N = s->n_values;
+    void *bp = nullptr, *bq = nullptr;
+    u64 *csum = nullptr;
+    if (s->counted) {
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_COUNT_POS, (N + 1) * 8, &bp));
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_COUNT_SCAN, (scan_parts(N) + 8) * 8, &bq));
+        csum = static_cast<u64 *>(bp);
+        u64 *tot = static_cast<u64 *>(bq);
+        HIPCHK(ctx, scan_counts(st, KeepOf{s->counts}, N, tot + 8, csum, tot, (u64 *)nullptr));
+    }
+    hipLaunchKernelGGL(k_ct_totals, dim3(ct_grid(ctx, count)), dim3(256), 0, st, (const u64 *)(s->offsets + first), (const u64 *)csum, count, out);
+    HIPCHK(ctx, hipGetLastError());
+    return BSK_OK;
+}
+
+int sets_sumsq_device(bsk_ctx *ctx, const bsk_sets *s, u64 first, u64 count, u64 *out) {
+    hipStream_t st = ctx->stream;
+    const u64 *offs = s->offsets + first;
+    if (!s->counted) {  // every count is 1: the sizes
+        hipLaunchKernelGGL(k_ct_totals, dim3(ct_grid(ctx, count)), dim3(256), 0, st, offs, (const u64 *)nullptr, count, out);
+    } else if (s->n_values <= s->n_sets * 16) {  // small sets (16 values on average): 8 lanes a set
+        hipLaunchKernelGGL(k_ct_sumsq<8>, dim3(ct_grid(ctx, count * 8)), dim3(256), 0, st, offs, (const u32 *)s->counts, count, out);
+    } else {  // a wavefront a set
+        hipLaunchKernelGGL(k_ct_sumsq<64>, dim3(ct_grid(ctx, count * 64)), dim3(256), 0, st, offs, (const u32 *)s->counts, count, out);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return BSK_OK;
+}
+
 extern "C" int bsk_sets_counts_device(const bsk_sets *s, const uint32_t **counts) {
     if (!s || !counts) return BSK_ERR_ARG;
     *counts = s->counted ? (const uint32_t *)s->counts : nullptr;
@@ -273,22 +306,12 @@ extern "C" int bsk_sets_totals(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, 
     if (first > s->n_sets || count > s->n_sets - first) return fail_arg(ctx, "bsk_sets_totals: range outside the sets");
     if (count == 0) return BSK_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const u64 N = s->n_values;
-    void *bo = nullptr, *bp = nullptr, *bq = nullptr;
+    void *bo = nullptr;
     HIPCHK(ctx, ctx_pool(ctx, SLOT_COUNT_OUT, count * 8, &bo));
-    u64 *csum = nullptr;
-    if (s->counted) {
-        HIPCHK(ctx, ctx_pool(ctx, SLOT_COUNT_POS, (N + 1) * 8, &bp));
-        HIPCHK(ctx, ctx_pool(ctx, SLOT_COUNT_SCAN, (scan_parts(N) + 8) * 8, &bq));
-        csum = static_cast<u64 *>(bp);
-        u64 *tot = static_cast<u64 *>(bq);
-        HIPCHK(ctx, scan_counts(st, KeepOf{s->counts}, N, tot + 8, csum, tot, (u64 *)nullptr));
-    }
-    hipLaunchKernelGGL(k_ct_totals, dim3(ct_grid(ctx, count)), dim3(256), 0, st, (const u64 *)(s->offsets + first), (const u64 *)csum, count, static_cast<u64 *>(bo));
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(totals, bo, count * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    const int rc = sets_totals_device(ctx, s, first, count, static_cast<u64 *>(bo));
+    if (rc != BSK_OK) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(totals, bo, count * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return BSK_OK;
 }
 
@@ -298,19 +321,11 @@ extern "C" int bsk_sets_sumsq(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, u
     if (first > s->n_sets || count > s->n_sets - first) return fail_arg(ctx, "bsk_sets_sumsq: range outside the sets");
     if (count == 0) return BSK_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
     void *bo = nullptr;
     HIPCHK(ctx, ctx_pool(ctx, SLOT_COUNT_OUT, count * 8, &bo));
-    const u64 *offs = s->offsets + first;
-    if (!s->counted) {  // every count is 1: the sizes
-        hipLaunchKernelGGL(k_ct_totals, dim3(ct_grid(ctx, count)), dim3(256), 0, st, offs, (const u64 *)nullptr, count, static_cast<u64 *>(bo));
-    } else if (s->n_values <= s->n_sets * 16) {  // small sets (16 values on average): 8 lanes a set
-        hipLaunchKernelGGL(k_ct_sumsq<8>, dim3(ct_grid(ctx, count * 8)), dim3(256), 0, st, offs, (const u32 *)s->counts, count, static_cast<u64 *>(bo));
-    } else {  // a wavefront a set
-        hipLaunchKernelGGL(k_ct_sumsq<64>, dim3(ct_grid(ctx, count * 64)), dim3(256), 0, st, offs, (const u32 *)s->counts, count, static_cast<u64 *>(bo));
-    }
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(sumsq, bo, count * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    const int rc = sets_sumsq_device(ctx, s, first, count, static_cast<u64 *>(bo));
+    if (rc != BSK_OK) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(sumsq, bo, count * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return BSK_OK;
 }

@@ -76,7 +76,9 @@ enum PoolSlot {
     SLOT_WIN_SEQS = 52, SLOT_WIN_SPANS = 53,
     // folded hits (fold.hip): the target-to-group map; the group offsets, heads, runs and their scans
     SLOT_FOLD_MAP = 54, SLOT_FOLD_WORK = 55,
-    POOL_SLOTS = 56
+    // weighted containment search (search.hip): the payload pass's chunk offsets, scan parts and figures; the saturation bits of its hits
+    SLOT_SW_QUERY = 56, SLOT_SW_FLAGS = 57,
+    POOL_SLOTS = 58
 };
 
 struct bsk_ctx {

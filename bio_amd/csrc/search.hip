@@ -17,6 +17,11 @@
 // counts and a move.  Queries whose sum exceeds the LDS budget (SR_CAP: a genome against genomes, a value held by thousands of
 // targets) are listed and take the large path: (slot << 32) | target keys, the rocprim::radix_sort_keys<u64> sets.hip already
 // instantiates, run-length, threshold.  Exact, and no new template.
+//
+// With counts (bsk_index_build_counted, bsk_index_search_counted): the build sorts (key, posting number) with the same instantiation and one
+// gather fills post_tgt and post_cnt from the permutation; the search runs as it is, and a payload pass over rng[] and the finished rows adds
+// cq * ct and min(cq, ct) of every posting whose target the row lists -- in LDS for small-path rows of at most SW_ROW hits (k_sw_row), with
+// 64-bit atomics for chunks of SW_CHUNK values of everything else (k_sw_chunk).  DESIGN.md 3.16.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -44,16 +49,25 @@ struct IndexArrays {
     u32 *post_tgt = nullptr;   // [P] target ids, ascending inside a key
     u32 *dir = nullptr;        // [2^bits + 1] first key of every bucket
     u32 *tsize = nullptr;      // [n_targets] |t|
+    // a counted index (bsk_index_build_counted of counted sets) only; NULL otherwise
+    u32 *post_cnt = nullptr;   // [P] the target's count of the key's value, parallel to post_tgt
+    u64 *tsumsq = nullptr;     // [n_targets] sum of t's squared counts, saturating (bsk_sets_sumsq)
+    u64 *ttotal = nullptr;     // [n_targets] sum of t's counts (bsk_sets_totals)
 };
 struct bsk_index {
     bsk_ctx *ctx = nullptr;    // the context this handle is searched on (never dereferenced by a release: it may be gone by then)
     u64 n_targets = 0, n_postings = 0, n_distinct = 0, max_bucket = 0, device_bytes = 0;
     int bits = 0;              // directory over the top `bits` bits of the mixed key
+    bool counted = false;      // the arrays hold post_cnt, tsumsq and ttotal
     IndexArrays *a = nullptr;
 };
 
 #define SR_CAP 2048  // target ids pass C holds per query: 8 KB of LDS per wavefront
 #define SR_WAVES 4   // wavefronts per workgroup of pass C
+// the payload pass of bsk_index_search_counted
+#define SW_ROW 512    // hits of a small-path query whose (target, dot, min_sum) row one wavefront holds in LDS: 10 KB
+#define SW_WAVES 4    // wavefronts per workgroup of k_sw_row: 40 KB of LDS, four workgroups a CU
+#define SW_CHUNK 256  // query values one wavefront of k_sw_chunk walks (four trips of 64 lanes)
 
 namespace {
 
@@ -124,6 +138,18 @@ __global__ __launch_bounds__(256) void k_ix_maxb(const u32 *dir, u64 nb, u64 *mx
     }
     m = wave_max_u32(m);
     if ((threadIdx.x & 63) == 0 && m) atomicMax((unsigned long long *)mx, (unsigned long long)m);
+}
+// the counted build sorts (key, posting number) instead of (key, target): ord[i] = i going in, the permutation coming out -- the sort is
+// stable, so the postings of a key leave in posting order, which is target order -- and one gather fills both posting arrays from it
+__global__ __launch_bounds__(256) void k_ix_ord(u64 P, u32 *ord) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (u64)gridDim.x * blockDim.x) ord[i] = (u32)i;
+}
+__global__ __launch_bounds__(256) void k_ix_gather(const u32 *perm, const u32 *tgt, const u32 *cnt, u64 P, u32 *post_tgt, u32 *post_cnt) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (u64)gridDim.x * blockDim.x) {
+        const u32 j = perm[i];  // < P: a permutation of 0 .. P - 1
+        post_tgt[i] = tgt[j];
+        post_cnt[i] = cnt[j];
+    }
 }
 
 // ---- search ----
@@ -326,6 +352,120 @@ __global__ __launch_bounds__(256) void k_sr_move(const u64 *stage_off, const u64
             sh[d0 + i] = st_sh[s0 + i];
         }
     }
+}
+
+// ---- the payload pass of bsk_index_search_counted: dot and min_sum of every listed pair ----
+// The search has finished: rng[] and qsum[] are still in the pool, the hits' rows are in place.  For every posting (t, ct) of every query
+// value (v, cq) the pass looks t up in the query's row (its targets ascend: a binary search) and, where t is listed, adds cq * ct to the
+// hit's dot and min(cq, ct) to its min_sum.  Integer adds commute, so the order the lanes arrive in does not show.  An add to dot that
+// wraps (old + x < old) happens iff the true sum reaches 2^64: it sets the hit's sticky bit, and the hit's dot becomes 2^64 - 1.
+struct SwRow {
+    const u32 *tg;  // the row's targets, ascending
+    u64 *d, *m;     // its dot and min_sum
+    u32 *f;         // sticky saturation bits: bit (f0 + j) & 31 of word (f0 + j) >> 5 for hit j of the row
+    u64 f0;
+    u32 h;          // hits of the row
+    __device__ __forceinline__ void add(u32 t, u32 cq, u32 ct) const {
+        u32 lo = 0, hi = h;
+        while (lo < hi) {
+            const u32 mid = (lo + hi) >> 1;
+            if (tg[mid] < t) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo < h && tg[lo] == t) {
+            const u64 x = (u64)cq * ct;
+            const u64 old = atomicAdd((unsigned long long *)&d[lo], (unsigned long long)x);
+            if (old + x < old) atomicOr(&f[(f0 + lo) >> 5], 1u << ((f0 + lo) & 31));
+            atomicAdd((unsigned long long *)&m[lo], (unsigned long long)(cq < ct ? cq : ct));
+        }
+    }
+};
+// the postings of query values [a, e) against `row`, 64 values a trip: a lane walks its value's list, lists longer than 64 are walked by the
+// whole wavefront (as k_lg_emit copies them).  qcnt / post_cnt == NULL: an uncounted operand, every count 1.
+__device__ __forceinline__ void sw_walk(const u64 *rng, const u32 *qcnt, u64 a, u64 e, int lane, const u32 *post_tgt, const u32 *post_cnt, const SwRow &row) {
+    for (u64 i0 = a; i0 < e; i0 += 64) {
+        const u64 i = i0 + lane;
+        const u64 r = i < e ? rng[i] : 0;
+        const u32 len = (u32)r, s = (u32)(r >> 32);
+        const u32 cq = (qcnt && i < e) ? qcnt[i] : 1u;
+        if (len <= 64)
+            for (u32 t = 0; t < len; ++t) row.add(post_tgt[s + t], cq, post_cnt ? post_cnt[s + t] : 1u);
+        u64 big = __ballot(len > 64);
+        while (big) {
+            const int src = __builtin_ctzll(big);
+            big &= big - 1;
+            const u32 s2 = (u32)__builtin_amdgcn_readlane((int)s, src), len2 = (u32)__builtin_amdgcn_readlane((int)len, src),
+                      cq2 = (u32)__builtin_amdgcn_readlane((int)cq, src);
+            for (u32 t = lane; t < len2; t += 64) row.add(post_tgt[s2 + t], cq2, post_cnt ? post_cnt[s2 + t] : 1u);
+        }
+    }
+}
+// which kernel a query with hits takes: k_sw_row when it was on the search's small path and its row fits the LDS row, else k_sw_chunk
+__device__ __forceinline__ bool sw_in_lds(u64 qsum, u64 h) { return qsum <= SR_CAP && h <= SW_ROW; }
+struct SwRowsOf {  // 1 for a query of k_sw_row
+    const u64 *qsum, *hoff;
+    __device__ __forceinline__ u64 operator()(u64 q) const {
+        const u64 h = hoff[q + 1] - hoff[q];
+        return h && sw_in_lds(qsum[q], h) ? 1 : 0;
+    }
+};
+struct SwChunksOf {  // the chunks of SW_CHUNK values a query of k_sw_chunk is cut into
+    const u64 *qsum, *hoff, *qoff;
+    __device__ __forceinline__ u64 operator()(u64 q) const {
+        const u64 h = hoff[q + 1] - hoff[q];
+        return h && !sw_in_lds(qsum[q], h) ? (qoff[q + 1] - qoff[q] + SW_CHUNK - 1) / SW_CHUNK : 0;
+    }
+};
+// one wavefront per query: the row's targets and zeroed accumulators in LDS, the walk, one coalesced write of the finished row
+__global__ __launch_bounds__(64 * SW_WAVES) void k_sw_row(const u64 *qoff, const u64 *rng, const u64 *qsum, u64 nq, const u32 *qcnt, const u32 *post_tgt,
+                                                          const u32 *post_cnt, const u64 *hoff, const u32 *htgt, u64 *dot, u64 *msum) {
+    __shared__ u64 s_d[SW_WAVES][SW_ROW], s_m[SW_WAVES][SW_ROW];
+    __shared__ u32 s_t[SW_WAVES][SW_ROW], s_f[SW_WAVES][SW_ROW / 32];
+    static_assert(SW_ROW % 32 == 0 && SW_ROW / 32 <= 64 && SW_ROW <= SR_CAP, "a lane per word of saturation bits; a small-path row has at most SR_CAP hits");
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((u64)gridDim.x * blockDim.x) >> 6;
+    for (u64 q = wave; q < nq; q += nw) {
+        const u64 h0 = hoff[q], h64 = hoff[q + 1] - h0;
+        if (h64 == 0 || !sw_in_lds(qsum[q], h64)) continue;  // (the same for every lane)
+        const u32 h = (u32)h64;  // <= SW_ROW
+        for (u32 j = lane; j < h; j += 64) {
+            s_t[w][j] = htgt[h0 + j];
+            s_d[w][j] = 0;
+            s_m[w][j] = 0;
+        }
+        if (lane < SW_ROW / 32) s_f[w][lane] = 0;
+        wave_sync_lds();
+        sw_walk(rng, qcnt, qoff[q], qoff[q + 1], lane, post_tgt, post_cnt, SwRow{s_t[w], s_d[w], s_m[w], s_f[w], 0, h});
+        wave_sync_lds();
+        for (u32 j = lane; j < h; j += 64) {
+            dot[h0 + j] = ((s_f[w][j >> 5] >> (j & 31)) & 1u) ? ~0ULL : s_d[w][j];
+            msum[h0 + j] = s_m[w][j];
+        }
+        wave_sync_lds();  // every lane is done with the row before the next query fills it
+    }
+}
+// one wavefront per chunk of SW_CHUNK values of a query: its query by a binary search over the chunk offsets (coff[q] <= c < coff[q + 1]; a
+// query without chunks has coff[q] == coff[q + 1] and is never found), the adds as 64-bit atomics into the zeroed global row
+__global__ __launch_bounds__(256) void k_sw_chunk(const u64 *qoff, const u64 *rng, const u64 *coff, u64 nq, u64 nc, const u32 *qcnt, const u32 *post_tgt,
+                                                  const u32 *post_cnt, const u64 *hoff, const u32 *htgt, u64 *dot, u64 *msum, u32 *flags) {
+    const int lane = threadIdx.x & 63;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = ((u64)gridDim.x * blockDim.x) >> 6;
+    for (u64 c = wave; c < nc; c += nw) {
+        u64 lo = 0, hi = nq;  // nc != 0: nq != 0.  The last query whose first chunk is <= c
+        while (hi - lo > 1) {
+            const u64 mid = (lo + hi) >> 1;
+            if (coff[mid] <= c) lo = mid;
+            else hi = mid;
+        }
+        const u64 a = qoff[lo] + (c - coff[lo]) * SW_CHUNK, end = qoff[lo + 1], e = a + SW_CHUNK < end ? a + SW_CHUNK : end;
+        const u64 h0 = hoff[lo];
+        sw_walk(rng, qcnt, a, e, lane, post_tgt, post_cnt, SwRow{htgt + h0, dot + h0, msum + h0, flags, h0, (u32)(hoff[lo + 1] - h0)});
+    }
+}
+// dot = min(true sum, 2^64 - 1): the hits whose sticky bit is set
+__global__ __launch_bounds__(256) void k_sw_finish(const u32 *flags, u64 H, u64 *dot) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < H; i += (u64)gridDim.x * blockDim.x)
+        if ((flags[i >> 5] >> (i & 31)) & 1u) dot[i] = ~0ULL;
 }
 
 // ---- the n best hits of every query (bsk_hits_top) ----
@@ -586,6 +726,9 @@ extern "C" void bsk_index_release(bsk_index *ix) {
         (void)hipFree(a->post_tgt);
         (void)hipFree(a->dir);
         (void)hipFree(a->tsize);
+        (void)hipFree(a->post_cnt);
+        (void)hipFree(a->tsumsq);
+        (void)hipFree(a->ttotal);
         delete a;
     }
     delete ix;
@@ -625,20 +768,33 @@ extern "C" int bsk_index_attach(bsk_ctx *ctx, const bsk_index *ix, bsk_index **h
     HIPCHK(ctx, hipMemcpyPeer(d->post_tgt, d->device, src->post_tgt, src->device, b_tgt));
     HIPCHK(ctx, hipMemcpyPeer(d->dir, d->device, src->dir, src->device, b_dir));
     HIPCHK(ctx, hipMemcpyPeer(d->tsize, d->device, src->tsize, src->device, b_ts));
+    if (ix->counted) {  // a counted index: its counts and norms go along
+        const size_t b_norm = (T ? T : 1) * 8;
+        HIPCHK(ctx, hipMalloc(&d->post_cnt, b_tgt));
+        HIPCHK(ctx, hipMalloc(&d->tsumsq, b_norm));
+        HIPCHK(ctx, hipMalloc(&d->ttotal, b_norm));
+        HIPCHK(ctx, hipMemcpyPeer(d->post_cnt, d->device, src->post_cnt, src->device, b_tgt));
+        HIPCHK(ctx, hipMemcpyPeer(d->tsumsq, d->device, src->tsumsq, src->device, b_norm));
+        HIPCHK(ctx, hipMemcpyPeer(d->ttotal, d->device, src->ttotal, src->device, b_norm));
+    }
     HIPCHK(ctx, hipDeviceSynchronize());
     *handle = hold.release();
     return BSK_OK;
 }
 
-extern "C" int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index **out) {
+// bsk_index_build (keep_counts == false) and bsk_index_build_counted: the same checks, limits and slot rule under the entry's own name; with
+// counts the sort carries the posting number instead of the target and k_ix_gather fills post_tgt and post_cnt from the permutation
+static int index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index **out, bool keep_counts) {
     if (out) *out = nullptr;
-    if (!ctx || !targets || !out) return fail_arg(ctx, "bsk_index_build: null argument");
-    if (targets->ctx != ctx) return fail_arg(ctx, "bsk_index_build: the sets belong to another context");
+    if (!ctx || !targets || !out) return fail_arg(ctx, keep_counts ? "bsk_index_build_counted: null argument" : "bsk_index_build: null argument");
+    if (targets->ctx != ctx)
+        return fail_arg(ctx, keep_counts ? "bsk_index_build_counted: the sets belong to another context" : "bsk_index_build: the sets belong to another context");
     const u64 T = targets->n_sets, P = targets->n_values;
     if (T >= (1ULL << 32) || P >= (1ULL << 32)) {
-        ctx->err = "bsk_index_build: 2^32 targets or postings or more";
+        ctx->err = keep_counts ? "bsk_index_build_counted: 2^32 targets or postings or more" : "bsk_index_build: 2^32 targets or postings or more";
         return BSK_ERR_UNSUPPORTED;
     }
+    const bool counted = keep_counts && targets->counted;  // uncounted sets: an index without counts, whichever entry built it
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     bsk_index *ix = new (std::nothrow) bsk_index();
@@ -652,9 +808,20 @@ extern "C" int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index 
     ix->n_postings = P;
     Temps tmp;
     u64 *kin = nullptr, *kout = nullptr, *pos = nullptr, *part = nullptr, *tot = nullptr;
-    u32 *tin = nullptr, *flag = nullptr;
+    u32 *tin = nullptr, *flag = nullptr, *ord = nullptr, *perm = nullptr;
     HIPCHK(ctx, hipMalloc(&ix->a->post_tgt, (P ? P : 1) * 4));
     HIPCHK(ctx, hipMalloc(&ix->a->tsize, (T ? T : 1) * 4));
+    if (counted) {
+        ix->counted = true;
+        HIPCHK(ctx, hipMalloc(&ix->a->post_cnt, (P ? P : 1) * 4));
+        HIPCHK(ctx, hipMalloc(&ix->a->tsumsq, (T ? T : 1) * 8));
+        HIPCHK(ctx, hipMalloc(&ix->a->ttotal, (T ? T : 1) * 8));
+        if (T) {  // the norms, as bsk_sets_sumsq and bsk_sets_totals give them (on the stream; the read-backs below wait for them)
+            int rc = sets_sumsq_device(ctx, targets, 0, T, ix->a->tsumsq);
+            if (rc == BSK_OK) rc = sets_totals_device(ctx, targets, 0, T, ix->a->ttotal);
+            if (rc != BSK_OK) return rc;
+        }
+    }
     HIPCHK(ctx, tmp.get((void **)&tot, 64));
     HIPCHK(ctx, hipMemsetAsync(tot, 0, 64, st));
     if (T) {
@@ -668,11 +835,22 @@ extern "C" int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index 
         HIPCHK(ctx, tmp.get((void **)&tin, P * 4));
         hipLaunchKernelGGL(k_ix_pairs, dim3(grid_for(ctx, P, 256, 16)), dim3(256), 0, st, targets->offsets, targets->values, T, P, kin, tin);
         HIPCHK(ctx, hipGetLastError());
+        if (counted) {
+            HIPCHK(ctx, tmp.get((void **)&ord, P * 4));
+            HIPCHK(ctx, tmp.get((void **)&perm, P * 4));
+            hipLaunchKernelGGL(k_ix_ord, dim3(grid_for(ctx, P, 256, 16)), dim3(256), 0, st, P, ord);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        u32 *vin = counted ? ord : tin, *vout = counted ? perm : ix->a->post_tgt;
         size_t tb = 0;
-        HIPCHK(ctx, rocprim::radix_sort_pairs(nullptr, tb, kin, kout, tin, ix->a->post_tgt, (size_t)P, 0, 64, st));
+        HIPCHK(ctx, rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, (size_t)P, 0, 64, st));
         void *stmp = nullptr;
         HIPCHK(ctx, tmp.get(&stmp, tb));
-        HIPCHK(ctx, rocprim::radix_sort_pairs(stmp, tb, kin, kout, tin, ix->a->post_tgt, (size_t)P, 0, 64, st));
+        HIPCHK(ctx, rocprim::radix_sort_pairs(stmp, tb, kin, kout, vin, vout, (size_t)P, 0, 64, st));
+        if (counted) {
+            hipLaunchKernelGGL(k_ix_gather, dim3(grid_for(ctx, P, 256, 16)), dim3(256), 0, st, perm, tin, targets->counts, P, ix->a->post_tgt, ix->a->post_cnt);
+            HIPCHK(ctx, hipGetLastError());
+        }
         flag = tin;  // (both free after the sort)
         pos = kin;
         HIPCHK(ctx, tmp.get((void **)&part, (scan_parts(P)) * 8));
@@ -702,7 +880,40 @@ extern "C" int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index 
     HIPCHK(ctx, read_back(ctx, tot + 1, 1, 1));
     ix->max_bucket = ctx->h_pinned[1];
     ix->device_bytes = (U ? U : 1) * 8 + (U + 1) * 4 + (P ? P : 1) * 4 + (nb + 1) * 4 + (T ? T : 1) * 4;
+    if (counted) ix->device_bytes += (P ? P : 1) * 4 + 2 * (T ? T : 1) * 8;
     *out = hold.release();
+    return BSK_OK;
+}
+
+extern "C" int bsk_index_build(bsk_ctx *ctx, const bsk_sets *targets, bsk_index **out) { return index_build(ctx, targets, out, false); }
+extern "C" int bsk_index_build_counted(bsk_ctx *ctx, const bsk_sets *targets, bsk_index **out) { return index_build(ctx, targets, out, true); }
+
+extern "C" int bsk_index_counted(const bsk_index *ix, int *counted) {
+    if (!ix || !counted) return BSK_ERR_ARG;
+    *counted = ix->counted ? 1 : 0;
+    return BSK_OK;
+}
+
+// the norms of targets first .. first + count - 1: the arrays a counted index keeps, |t| for an index without counts
+extern "C" int bsk_index_fetch_norms(bsk_ctx *ctx, const bsk_index *ix, uint64_t first, uint64_t count, uint64_t *sumsq, uint64_t *totals) {
+    if (!ctx || !ix) return fail_arg(ctx, "bsk_index_fetch_norms: null argument");
+    if (ix->ctx != ctx) return fail_arg(ctx, "bsk_index_fetch_norms: the index belongs to another context");
+    if (first > ix->n_targets || count > ix->n_targets - first) return fail_arg(ctx, "bsk_index_fetch_norms: range outside the targets");
+    if (count == 0 || (!sumsq && !totals)) return BSK_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ix->counted) {
+        if (sumsq) HIPCHK(ctx, hipMemcpyAsync(sumsq, ix->a->tsumsq + first, count * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (totals) HIPCHK(ctx, hipMemcpyAsync(totals, ix->a->ttotal + first, count * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return BSK_OK;
+    }
+    std::vector<u32> sz(count);
+    HIPCHK(ctx, hipMemcpyAsync(sz.data(), ix->a->tsize + first, count * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (u64 t = 0; t < count; ++t) {
+        if (sumsq) sumsq[t] = sz[t];
+        if (totals) totals[t] = sz[t];
+    }
     return BSK_OK;
 }
 
@@ -772,19 +983,49 @@ extern "C" int bsk_hits_from_host(bsk_ctx *ctx, const uint64_t *offsets, uint64_
 }
 
 static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, const bsk_search_params *sp, bsk_hits *res);
-extern "C" int bsk_index_search(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *queries, const bsk_search_params *sp, bsk_hits **hits) {
-    if (!ctx || !ix || !queries || !sp || !hits) return fail_arg(ctx, "bsk_index_search: null argument");
+static int weights_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, bsk_hits *res);
+// bsk_index_search and bsk_index_search_counted: the same checks in the same order, each under the entry's own name, all before the slot is
+// taken over; the weighted entry runs the search as it is and then the payload pass over what the search left in the pool
+static int search_entry(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *queries, const bsk_search_params *sp, bsk_hits **hits, bool weighted) {
+    if (!ctx || !ix || !queries || !sp || !hits) return fail_arg(ctx, weighted ? "bsk_index_search_counted: null argument" : "bsk_index_search: null argument");
     if (ix->ctx != ctx || queries->ctx != ctx || (*hits && (*hits)->ctx != ctx))
-        return fail_arg(ctx, "bsk_index_search: the index, the queries or the hits belong to another context");
-    if (sp->reserved != 0) return fail_arg(ctx, "bsk_index_search: reserved != 0");
+        return fail_arg(ctx, weighted ? "bsk_index_search_counted: the index, the queries or the hits belong to another context"
+                                      : "bsk_index_search: the index, the queries or the hits belong to another context");
+    if (sp->reserved != 0) return fail_arg(ctx, weighted ? "bsk_index_search_counted: reserved != 0" : "bsk_index_search: reserved != 0");
     if (!(sp->min_query_cov >= 0.0 && sp->min_query_cov <= 1.0) || !(sp->min_target_cov >= 0.0 && sp->min_target_cov <= 1.0))
-        return fail_arg(ctx, "bsk_index_search: a cover outside 0..1 (or NaN)");
+        return fail_arg(ctx, weighted ? "bsk_index_search_counted: a cover outside 0..1 (or NaN)" : "bsk_index_search: a cover outside 0..1 (or NaN)");
     if (queries->n_sets >= (1ULL << 32) || queries->n_values >= (1ULL << 32)) {
-        ctx->err = "bsk_index_search: 2^32 query sets or query values or more (split the queries)";
+        ctx->err = weighted ? "bsk_index_search_counted: 2^32 query sets or query values or more (split the queries)"
+                            : "bsk_index_search: 2^32 query sets or query values or more (split the queries)";
         return BSK_ERR_UNSUPPORTED;
     }
-    return take_over(ctx, hits, bsk_hits_release, [&](bsk_hits *res, bool) { return search_impl(ctx, ix, queries, sp, res); });
+    return take_over(ctx, hits, bsk_hits_release, [&](bsk_hits *res, bool) {
+        const int rc = search_impl(ctx, ix, queries, sp, res);
+        return rc != BSK_OK || !weighted ? rc : weights_impl(ctx, ix, queries, res);
+    });
 }
+extern "C" int bsk_index_search(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *queries, const bsk_search_params *sp, bsk_hits **hits) {
+    return search_entry(ctx, ix, queries, sp, hits, false);
+}
+extern "C" int bsk_index_search_counted(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *queries, const bsk_search_params *sp, bsk_hits **hits) {
+    return search_entry(ctx, ix, queries, sp, hits, true);
+}
+
+// the per-query arrays of one search, one carved buffer of SLOT_SEARCH_QUERY: search_impl fills them, weights_impl reads qsum again
+struct SearchCarve {
+    Carve c;
+    size_t o_qsum, o_stage, o_hcnt, o_lslot, o_loff, o_part, o_tot, o_lq;
+    explicit SearchCarve(u64 nq) {
+        o_qsum = c.add<u64>(nq);
+        o_stage = c.add<u64>(nq + 1);
+        o_hcnt = c.add<u64>(nq);
+        o_lslot = c.add<u64>(nq + 1);
+        o_loff = c.add<u64>(nq + 1);
+        o_part = c.add<u64>(scan_parts(nq));
+        o_tot = c.add<u64>(8);
+        o_lq = c.add<u32>(nq);
+    }
+};
 
 static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, const bsk_search_params *sp, bsk_hits *res) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -799,16 +1040,13 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
     res->has_members = false;  // (... and the members of folded hits)
     HIPCHK(ctx, grow_array(&res->offsets, &res->c_offsets, (nq + 1) * 8));
     // per-query arrays (one carved buffer) and the query values' posting ranges
-    Carve cq;
-    const size_t o_qsum = cq.add<u64>(nq), o_stage = cq.add<u64>(nq + 1), o_hcnt = cq.add<u64>(nq), o_lslot = cq.add<u64>(nq + 1),
-                 o_loff = cq.add<u64>(nq + 1), o_part = cq.add<u64>(scan_parts(nq)), o_tot = cq.add<u64>(8),
-                 o_lq = cq.add<u32>(nq);
+    const SearchCarve cq(nq);
     void *bq = nullptr, *brng = nullptr;
-    HIPCHK(ctx, ctx_pool(ctx, SLOT_SEARCH_QUERY, cq.bytes, &bq));
+    HIPCHK(ctx, ctx_pool(ctx, SLOT_SEARCH_QUERY, cq.c.bytes, &bq));
     HIPCHK(ctx, ctx_pool(ctx, SLOT_SEARCH_RANGES, (nv ? nv : 1) * 8, &brng));
-    u64 *qsum = at<u64>(bq, o_qsum), *stage_off = at<u64>(bq, o_stage), *hcnt = at<u64>(bq, o_hcnt), *lslot = at<u64>(bq, o_lslot),
-        *loff = at<u64>(bq, o_loff), *part = at<u64>(bq, o_part), *tot = at<u64>(bq, o_tot), *rng = static_cast<u64 *>(brng);
-    u32 *lq = at<u32>(bq, o_lq);
+    u64 *qsum = at<u64>(bq, cq.o_qsum), *stage_off = at<u64>(bq, cq.o_stage), *hcnt = at<u64>(bq, cq.o_hcnt), *lslot = at<u64>(bq, cq.o_lslot),
+        *loff = at<u64>(bq, cq.o_loff), *part = at<u64>(bq, cq.o_part), *tot = at<u64>(bq, cq.o_tot), *rng = static_cast<u64 *>(brng);
+    u32 *lq = at<u32>(bq, cq.o_lq);
     HIPCHK(ctx, hipMemsetAsync(tot, 0, 64, st));  // [0] staging, [1] large target ids, [2] large queries, [3] large runs, [4] kept runs, [5] hits
     // A. lookups
     if (nq) {
@@ -879,6 +1117,59 @@ static int search_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, co
     res->n_large = NL;
     snprintf(res->plan, sizeof res->plan, "k_sr_lookup + k_sr_small (LDS sort, <= %d target ids per query); large path: %llu queries, %llu target ids",
              SR_CAP, (unsigned long long)NL, (unsigned long long)L);
+    return BSK_OK;
+}
+
+// The payload pass: res holds the finished hits of search_impl(ctx, ix, qs, ...), whose rng[] (SLOT_SEARCH_RANGES) and qsum[] (SLOT_SEARCH_QUERY)
+// are still in the pool -- nothing has run on this context since.  dot[] and msum[] of every hit; the thresholds have been applied already
+// and read shared alone.
+static int weights_impl(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *qs, bsk_hits *res) {
+    hipStream_t st = ctx->stream;
+    const u64 nq = qs->n_sets, nv = qs->n_values, H = res->n_hits;
+    HIPCHK(ctx, grow_array(&res->dot, &res->c_dot, (H ? H : 1) * 8));
+    HIPCHK(ctx, grow_array(&res->msum, &res->c_msum, (H ? H : 1) * 8));
+    u64 n_rows = 0, NC = 0;
+    if (H) {
+        const SearchCarve cq(nq);
+        void *bq = nullptr, *brng = nullptr, *bw = nullptr;
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_SEARCH_QUERY, cq.c.bytes, &bq));  // (both as large as the search took them: the buffers it filled)
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_SEARCH_RANGES, (nv ? nv : 1) * 8, &brng));
+        const u64 *qsum = at<u64>(bq, cq.o_qsum), *rng = static_cast<const u64 *>(brng);
+        Carve cw;
+        const size_t o_coff = cw.add<u64>(nq + 1), o_rows = cw.add<u64>(nq + 1), o_part = cw.add<u64>(scan_parts(nq)), o_tot = cw.add<u64>(8);
+        HIPCHK(ctx, ctx_pool(ctx, SLOT_SW_QUERY, cw.bytes, &bw));
+        u64 *coff = at<u64>(bw, o_coff), *rows = at<u64>(bw, o_rows), *part = at<u64>(bw, o_part), *tot = at<u64>(bw, o_tot);
+        HIPCHK(ctx, hipMemsetAsync(tot, 0, 64, st));  // [0] chunks of k_sw_chunk, [1] queries of k_sw_row
+        HIPCHK(ctx, scan_counts(st, SwChunksOf{qsum, res->offsets, qs->offsets}, nq, part, coff, tot + 0, (u64 *)nullptr));
+        HIPCHK(ctx, scan_counts(st, SwRowsOf{qsum, res->offsets}, nq, part, rows, tot + 1, (u64 *)nullptr));
+        HIPCHK(ctx, read_back(ctx, tot, 2));
+        NC = ctx->h_pinned[0];
+        n_rows = ctx->h_pinned[1];
+        const u32 *qcnt = qs->counted ? qs->counts : nullptr, *pcnt = ix->counted ? ix->a->post_cnt : nullptr;
+        u32 *flags = nullptr;
+        if (NC) {  // the rows of k_sw_chunk start from zero (those of k_sw_row are written whole)
+            HIPCHK(ctx, ctx_pool(ctx, SLOT_SW_FLAGS, (H / 32 + 1) * 4, &flags));
+            HIPCHK(ctx, hipMemsetAsync(flags, 0, (H / 32 + 1) * 4, st));
+            HIPCHK(ctx, hipMemsetAsync(res->dot, 0, H * 8, st));
+            HIPCHK(ctx, hipMemsetAsync(res->msum, 0, H * 8, st));
+        }
+        if (n_rows) {
+            hipLaunchKernelGGL(k_sw_row, dim3(grid_for(ctx, nq, SW_WAVES, 16)), dim3(64 * SW_WAVES), 0, st, qs->offsets, rng, qsum, nq, qcnt, ix->a->post_tgt, pcnt,
+                               res->offsets, res->target, res->dot, res->msum);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        if (NC) {
+            hipLaunchKernelGGL(k_sw_chunk, dim3(grid_for(ctx, NC, 4, 16)), dim3(256), 0, st, qs->offsets, rng, coff, nq, NC, qcnt, ix->a->post_tgt, pcnt, res->offsets,
+                               res->target, res->dot, res->msum, flags);
+            hipLaunchKernelGGL(k_sw_finish, dim3(grid_for(ctx, H, 256, 16)), dim3(256), 0, st, flags, H, res->dot);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        HIPCHK(ctx, hipStreamSynchronize(st));
+    }
+    res->has_weights = true;
+    const size_t at_ = strlen(res->plan);
+    snprintf(res->plan + at_, sizeof res->plan - at_, "; weights: k_sw_row %llu queries (<= %d hits), k_sw_chunk %llu chunks of %d values", (unsigned long long)n_rows, SW_ROW,
+             (unsigned long long)NC, SW_CHUNK);
     return BSK_OK;
 }
 

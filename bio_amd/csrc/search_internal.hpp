@@ -13,13 +13,14 @@ struct bsk_hits {
     u64 *offsets = nullptr;  // [n_queries + 1]
     u32 *target = nullptr, *shared = nullptr;
     size_t c_offsets = 0, c_target = 0, c_shared = 0;  // bytes allocated (grow-only when the object is re-used)
-    char plan[192] = "";
+    char plan[256] = "";
     // hits with totals (compare.hip: bsk_sets_neighbors): total[i] = the values walked for hit i.  `has_total` says whether the array is
     // valid: every entry that writes hits into this object without totals clears it and keeps the array (grow-only, like the others).
     u32 *total = nullptr;  // [n_hits]
     size_t c_total = 0;
     bool has_total = false;
-    // hits with weights (compare.hip: bsk_sets_neighbors_counted): dot[i] and msum[i] of hit i, as the cells of bsk_sets_compare_counted.
+    // hits with weights (compare.hip: bsk_sets_neighbors_counted; search.hip: bsk_index_search_counted): dot[i] and msum[i] of hit i, as the
+    // cells of bsk_sets_compare_counted.
     // `has_weights` follows the rule of `has_total`: whoever clears that clears this, and the arrays stay.
     u64 *dot = nullptr, *msum = nullptr;  // [n_hits]
     size_t c_dot = 0, c_msum = 0;

@@ -47,6 +47,11 @@ hipError_t sets_run_counts(hipStream_t st, const u64 *v, const u32 *keep, const 
 // the sets' counts array, grow-only (reuse: with slack)
 static inline hipError_t sets_grow_counts(bsk_sets *s, u64 n, bool slack) { return grow_array(&s->counts, &s->c_counts, (n ? n : 1) * 4, slack); }
 
+// counts.hip: per set of first .. first + count - 1 (count != 0, a range inside s) the sum of its counts / of its squared counts
+// (saturating), as bsk_sets_totals / bsk_sets_sumsq define them, into a device array on the context's stream; nothing is read back.
+int sets_totals_device(bsk_ctx *ctx, const bsk_sets *s, u64 first, u64 count, u64 *out) __attribute__((visibility("hidden")));
+int sets_sumsq_device(bsk_ctx *ctx, const bsk_sets *s, u64 first, u64 count, u64 *out) __attribute__((visibility("hidden")));
+
 // rocprim::radix_sort_keys<u64> over bits [begin_bit, end_bit) on `st` (sets.hip: the instantiation its whole-batch sets use).
 // tmp == nullptr: *tmp_bytes receives the temporary storage it needs.
 hipError_t sets_sort_u64(void *tmp, size_t &tmp_bytes, u64 *in, u64 *out, size_t n, unsigned begin_bit, unsigned end_bit, hipStream_t st)

@@ -481,6 +481,30 @@ class SearchIndex : public Owned<bsk_index, bsk_index_release> {
     int search(Engine &e, const DeviceSets &queries, const bsk_search_params &sp, SearchHits &into) const {
         return bsk_index_search(e.ctx(), p_, queries.get(), &sp, &into.handle());
     }
+    // build() with the targets' counts (bsk_index_build_counted): per posting the target's count, per target the norms; sets without
+    // counts give an index without counts
+    int build_counted(Engine &e, const DeviceSets &targets) {
+        bsk_index_release(p_);
+        p_ = nullptr;
+        return bsk_index_build_counted(e.ctx(), targets.get(), &p_);
+    }
+    bool counted() const {
+        int k = 0;
+        bsk_index_counted(p_, &k);
+        return k != 0;
+    }
+    // sumsq[t] and totals[t] of every target (bsk_index_fetch_norms); an index without counts reports the sizes for both
+    int fetch_norms(Engine &e, std::vector<uint64_t> &sumsq, std::vector<uint64_t> &totals) const {
+        uint64_t n = 0;
+        bsk_index_info(p_, &n, nullptr, nullptr, nullptr, nullptr);
+        sumsq.assign(n, 0);
+        totals.assign(n, 0);
+        return bsk_index_fetch_norms(e.ctx(), p_, 0, n, sumsq.data(), totals.data());
+    }
+    // search() with the counts (bsk_index_search_counted): the same hits, and per hit dot and min_sum (SearchHits::fetch_weights)
+    int search_counted(Engine &e, const DeviceSets &queries, const bsk_search_params &sp, SearchHits &into) const {
+        return bsk_index_search_counted(e.ctx(), p_, queries.get(), &sp, &into.handle());
+    }
     uint64_t max_bucket() const {
         uint64_t m = 0;
         bsk_index_info(p_, nullptr, nullptr, nullptr, &m, nullptr);

@@ -372,6 +372,13 @@ class Sets(_Owner):
         self.eng._chk(self.eng.lib.bsk_index_build(self.eng.ctx, self.h, C.byref(h)))
         return Index(self.eng, h, np.diff(self.offsets()))
 
+    def index_counted(self) -> "Index":
+        """index() with the sets' counts (bsk_index_build_counted): per posting the target's count of the value, per target the norms
+        (Index.norms()); search it with Index.search_counted.  Sets without counts give an index without counts."""
+        h = C.c_void_p()
+        self.eng._chk(self.eng.lib.bsk_index_build_counted(self.eng.ctx, self.h, C.byref(h)))
+        return Index(self.eng, h, np.diff(self.offsets()))
+
     # -- set algebra (bsk_sets_op / bsk_sets_reduce): the result is a Sets of the same engine, left on the device
     def _into(self, into: Optional["Sets"], call) -> "Sets":
         h = _take_over(self.eng, into, call)
@@ -683,9 +690,10 @@ class Index(_Owner):
 
     _release = "bsk_index_release"
 
-    def __init__(self, eng: "Engine", handle, target_sizes: np.ndarray):
+    def __init__(self, eng: "Engine", handle, target_sizes: np.ndarray, norms=None):
         self.eng, self.h = eng, handle
         self.target_sizes = np.asarray(target_sizes, np.uint64)
+        self._norms = norms  # (sumsq, totals) once norms() has fetched them; an attached handle inherits them
 
     def info(self):
         v = [C.c_uint64() for _ in range(5)]
@@ -702,12 +710,44 @@ class Index(_Owner):
         res._bind(h, np.diff(queries.offsets()), self.target_sizes)
         return res
 
+    @property
+    def counted(self) -> bool:
+        """whether the index keeps counts (bsk_index_counted): built by Sets.index_counted from counted sets"""
+        k = C.c_int()
+        self.eng._chk(self.eng.lib.bsk_index_counted(self.h, C.byref(k)))
+        return bool(k.value)
+
+    def norms(self):
+        """(sumsq, totals) of the targets, u64 each (bsk_index_fetch_norms), fetched once: what Sets.sumsq() and Sets.totals() gave for the
+        sets the index was built from; the targets' sizes for an index without counts"""
+        if self._norms is None:
+            n = self.info()["n_targets"]
+            q, t = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64)
+            self.eng._chk(self.eng.lib.bsk_index_fetch_norms(self.eng.ctx, self.h, 0, n, q.ctypes.data, t.ctypes.data))
+            self._norms = (q[:n], t[:n])
+        return self._norms
+
+    def search_counted(self, queries: Sets, min_shared: int = 1, min_query_cov: float = 0.0, min_target_cov: float = 0.0,
+                       reuse: Optional["Hits"] = None) -> "Hits":
+        """search() with the counts (bsk_index_search_counted): the same hits, bit for bit -- the thresholds read shared only -- and per
+        hit .dot and .min_sum over the values both sets hold, as Sets.compare_counted defines them with limit 0.  Queries or an index
+        without counts count 1 for every value.  The Hits are bound to the queries' sumsq() and totals() and the index's norms() -- fetched
+        when a formula first asks for them -- so cosine() and its kin work without the target sets; against an index without counts weighted_containment() is the share of
+        the query's mass found.  reuse: any Hits of this engine, whose device arrays are kept."""
+        sp = L.SearchParams(min_shared, 0, min_query_cov, min_target_cov)
+        h = _take_over(self.eng, reuse, lambda out: self.eng.lib.bsk_index_search_counted(self.eng.ctx, self.h, queries.h, C.byref(sp), out))
+        res = reuse if reuse is not None else Hits(self.eng)
+        res._bind(h, np.diff(queries.offsets()), self.target_sizes)
+        res._norm_source = lambda: (queries.sumsq(), self.norms()[0], queries.totals(), self.norms()[1])  # fetched when a formula first asks
+        res._plain_targets = not self.counted
+        return res
+
     def attach(self, engine: "Engine") -> "Index":
         """A handle on this index for another engine (bsk_index_attach): on the same device the arrays are shared, on another device
         they are copied there once.  Search it through the returned Index; the two may be closed in any order."""
         h = C.c_void_p()
         engine._chk(engine.lib.bsk_index_attach(engine.ctx, self.h, C.byref(h)))
-        return Index(engine, h, self.target_sizes)
+        return Index(engine, h, self.target_sizes, self._norms)
 
 
 class Hits(_Owner):
@@ -717,6 +757,8 @@ class Hits(_Owner):
     _totals = None  # total[] of hits with totals (Sets.neighbors), fetched with the others
     _members = None  # members[] of folded hits (Hits.fold), fetched with the others
     _weights = _norms = _operands = None  # the weighted side (Sets.neighbors_counted): (dot, min_sum), fetched with the others; (sumsq_a, sumsq_b, totals_a, totals_b); (a, b, limit)
+    _plain_targets = None  # Index.search_counted: whether the index kept no counts (weighted_containment() is defined there); None for any other hits
+    _norm_source = None  # Index.search_counted: () -> (sumsq_q, sumsq_t, totals_q, totals_t), from the queries and the index's own norms
 
     def __init__(self, eng: "Engine"):
         self.eng, self.h = eng, None
@@ -724,7 +766,7 @@ class Hits(_Owner):
 
     def _bind(self, h, query_sizes: np.ndarray, target_sizes: np.ndarray, operands=None):
         self.h, self._host, self._totals, self._members = h, None, None, None
-        self._weights, self._norms, self._operands = None, None, operands
+        self._weights, self._norms, self._operands, self._plain_targets, self._norm_source = None, None, operands, None, None
         self.query_sizes, self.target_sizes = query_sizes.astype(np.uint64), target_sizes
 
     def info(self):
@@ -937,7 +979,9 @@ class Hits(_Owner):
         gathered by query() and target"""
         self._cache()
         if self._weights is None:
-            raise ValueError("hits without weights: use Sets.neighbors_counted")
+            raise ValueError("hits without weights: use Sets.neighbors_counted or Index.search_counted")
+        if self._norms is None and self._norm_source is not None:
+            self._norms = self._norm_source()
         if self._norms is None:
             a, b, limit = self._operands
             if limit != 0:
@@ -976,6 +1020,19 @@ class Hits(_Owner):
         den = ta.astype(np.float64) + tb.astype(np.float64)
         out, nz = np.zeros_like(m), den != 0
         out[nz] = 1.0 - 2.0 * m[nz] / den[nz]
+        return out
+
+    def weighted_containment(self) -> np.ndarray:
+        """per hit dot / totals_q[i]: the share of the query's mass -- the sum of its counts -- that lies on values the target holds
+        (sourmash's abundance-weighted containment).  Defined for Index.search_counted against an index WITHOUT counts, where dot is
+        the sum of the query's counts over the shared values; any other hits raise.  NaN where dot is saturated."""
+        if self._plain_targets is None:
+            raise ValueError("weighted_containment is defined on the hits of Index.search_counted")
+        if not self._plain_targets:
+            raise ValueError("weighted_containment is defined against an index without counts (Sets.index): dot against a counted index is a product")
+        dt, _, _, _, ta, _ = self._whole("weighted_containment")
+        out = np.divide(dt.astype(np.float64), ta.astype(np.float64), out=np.zeros(dt.shape, np.float64), where=ta != 0)
+        out[dt == int(np.iinfo(np.uint64).max)] = np.nan
         return out
 
 

@@ -485,8 +485,8 @@ int bsk_result_sets(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk
  * arrays are kept and only grow.  Every such entry works in two steps.  What it checks BEFORE it takes the object over fails with the
  * slot as it was: the object is still the caller's, its contents intact.  Then the object is the entry's -- from here any failure
  * releases it and leaves the slot NULL, and BSK_OK stores it back.  Which error falls on which side:
- *   bsk_sets_op, _op_counted, _reduce, _filter_counts, _bottom and bsk_index_search: every BSK_ERR_ARG and the 2^32 limits
- *     (BSK_ERR_UNSUPPORTED) keep the slot; BSK_ERR_NOMEM and BSK_ERR_DEVICE release.
+ *   bsk_sets_op, _op_counted, _reduce, _filter_counts, _bottom, bsk_index_search and bsk_index_search_counted: every BSK_ERR_ARG and
+ *     the 2^32 limits (BSK_ERR_UNSUPPORTED) keep the slot; BSK_ERR_NOMEM and BSK_ERR_DEVICE release.
  *   bsk_hits_top: every BSK_ERR_ARG keeps the slot; its BSK_ERR_UNSUPPORTED (a sort key beyond 63 bits, known after a read-back),
  *     BSK_ERR_NOMEM and BSK_ERR_DEVICE release.
  *   bsk_sets_compare, _compare_counted: every BSK_ERR_ARG keeps the slot; both size limits (BSK_ERR_UNSUPPORTED) are checked after the
@@ -692,7 +692,8 @@ int bsk_sets_totals(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t co
  * Which route for an all-against-all: this one is dense -- its cost is the cells times the values a pair walks, whatever the sets
  * share -- and is the only one that gives the limit-bounded (Mash) numbers; it suits sketches of up to a few thousand values.
  * bsk_index_build + bsk_index_search is output-sparse -- its cost follows the postings and the pairs that share something -- and suits
- * whole sets (limit == 0 only) of many values of which most pairs share nothing.
+ * whole sets (limit == 0 only) of many values of which most pairs share nothing (with counts: bsk_index_build_counted +
+ * bsk_index_search_counted).
  * bsk_compare_plan: a short description that names the kernel and its tile shape; figures = {tiles run, rounds summed over the tiles,
  * most rounds of one tile} (a round stages one window of values per set of a tile).
  * bsk_compare_fetch: rows first_row .. first_row + n_rows - 1 to the host, n_rows * n_b cells each; BSK_ERR_ARG for a range outside
@@ -735,6 +736,48 @@ int bsk_compare_weights_device(const bsk_compare *c, const uint64_t **dot, const
 int bsk_compare_fetch_weights(bsk_ctx *ctx, const bsk_compare *c, uint64_t first_row, uint64_t n_rows,
                               uint64_t *dot, uint64_t *min_sum, uint64_t cell_cap);                       /* either array may be NULL */
 int bsk_sets_sumsq(bsk_ctx *ctx, const bsk_sets *s, uint64_t first, uint64_t count, uint64_t *sumsq /* host */);
+
+/* ---- weighted containment search: a counted index, dot and min_sum per hit ----
+ * The abundance-weighted form of bsk_index_build + bsk_index_search, the route whose cost follows the postings and not the cells: a
+ * counted sample (bsk_result_sets_counted) against an index of 10^5 genomes, or a panel of counted samples against itself.
+ * Definition.  For a listed pair (q, t) with V = q & t over the whole sets, cq(v) the query's count of v (1 for uncounted queries) and
+ * ct(v) the target's (1 for an index without counts):
+ *   dot     = min(sum over v in V of cq(v) * ct(v), 2^64-1)     (saturating; exactly this minimum, whatever the order of the adds)
+ *   min_sum = sum over v in V of min(cq(v), ct(v))              (exact: fewer than 2^32 values of counts below 2^32)
+ * -- the cells of bsk_sets_compare_counted and the weights of bsk_sets_neighbors_counted with limit == 0.  With both operands
+ * uncounted dot == min_sum == shared.
+ * bsk_index_build_counted is bsk_index_build plus a device array post_cnt[n_postings] (u32) parallel to the posting lists -- the
+ * target's count of the value -- and two per-target arrays, sumsq[n_targets] (u64, saturating, as bsk_sets_sumsq) and
+ * totals[n_targets] (u64, as bsk_sets_totals).  The index owns copies of everything, so the sets may be released.  Every array of
+ * bsk_index_build (keys, posting offsets, target ids, directory, sizes) and bits and max_bucket are bit-identical to bsk_index_build of
+ * the same sets; device_bytes grows by the new arrays.  Uncounted targets give an index without counts, exactly what bsk_index_build
+ * gives.  Limits, argument checks and *out ("only writes its slot": NULL on every error) are those of bsk_index_build, which itself is
+ * unchanged: given counted sets it still builds an index without counts.
+ * bsk_index_counted: *counted = 1 iff the index keeps counts.
+ * bsk_index_fetch_norms: sumsq and totals of targets first .. first + count - 1 to the host; either out array may be NULL; range and
+ * foreign-context rules of bsk_sets_totals.  An index without counts reports |t| for both.
+ * bsk_index_search_counted: offsets, target and shared are bit-identical to bsk_index_search with the same arguments -- the thresholds
+ * read shared only, the weights are a payload -- and the hits also carry dot[n_hits] and min_sum[n_hits] (bsk_hits_weights_device,
+ * bsk_hits_fetch_weights); they carry no totals and no members.  Any of the four combinations of counted and uncounted queries and index
+ * is legal.  The argument checks and their order (null, foreign context, reserved, covers), the 2^32 limits and the *hits rules are
+ * those of bsk_index_search ("The result slot" above).  After the search a payload pass visits every posting of every query value
+ * once more and looks its target up in the query's finished row: queries of the search's small path whose row holds at most 512 hits
+ * take a wavefront each and accumulate in LDS (k_sw_row); the others are cut into chunks of 256 query values that spread over the
+ * device and add with 64-bit atomics (k_sw_chunk).  Integer adds commute: the result is bit-identical from call to call.
+ * bsk_hits_plan gives the search's own text followed by "; weights: k_sw_row ... queries ..., k_sw_chunk ... chunks ..."; its count of
+ * large queries is the search's.
+ * On a counted index bsk_index_search, the pipeline's hits sink and bsk_index_info work exactly as on a plain one; bsk_index_attach
+ * shares the new arrays on the same device and copies them to another device.  Re-use: *hits may be any bsk_hits of this context;
+ * every entry that writes hits without weights (bsk_index_search, bsk_hits_top, bsk_hits_fold, the hits sink, ...) leaves the object
+ * without weights and keeps the arrays.  Not here: thresholds on the weighted measures, weights that survive bsk_hits_top or
+ * bsk_hits_fold, a weighted hits sink in the pipeline.
+ * What the numbers are for, with bsk_sets_sumsq / bsk_sets_totals of the queries and bsk_index_fetch_norms of the index: the cosine,
+ * the weighted Jaccard and the Bray-Curtis dissimilarity of every hit (formulas: bsk_sets_compare_counted); against an index without
+ * counts dot / totals(q) is the share of the query's k-mer mass that falls in the target. */
+int bsk_index_build_counted(bsk_ctx *ctx, const bsk_sets *targets, bsk_index **out);
+int bsk_index_counted(const bsk_index *ix, int *counted);
+int bsk_index_fetch_norms(bsk_ctx *ctx, const bsk_index *ix, uint64_t first, uint64_t count, uint64_t *sumsq, uint64_t *totals); /* either array may be NULL */
+int bsk_index_search_counted(bsk_ctx *ctx, const bsk_index *ix, const bsk_sets *queries, const bsk_search_params *sp, bsk_hits **hits);
 
 /* ---- window sets and folded hits: genome chunks as search targets ----
  * kmcp indexes one k-mer set per CHUNK of a reference (--split-number, --split-size, --split-overlap) and counts how many chunks of a
