@@ -120,8 +120,16 @@ def _take_over(eng: "Engine", into, call):
     rc = call(C.byref(h))
     if into is not None:
         into.h = h if h.value else None
+        if isinstance(into, Sets) and (rc == L.OK or not h.value):  # written or released: not what a result bound to it has seen
+            into._gen += 1
     eng._chk(rc)
     return h
+
+
+def _same_sets(sets, gens, what: str):
+    """the norms of a weighted result are those of its operands as the call saw them: fetched lazily, so only while the operands are unwritten"""
+    if any(x._gen != g for x, g in zip(sets, gens)):
+        raise ValueError(what + ": the operand sets were written or closed since the call; ask a formula before that (its norms are then kept)")
 
 
 def _chk_pipeline(lib, what: str, rc: int):
@@ -336,9 +344,14 @@ class Sets(_Owner):
 
     _release = "bsk_sets_release"
     group_offsets = None  # BatchResult.window_sets: the sets' windows by sequence (host, [n_reads + 1]); None on sets from any other call
+    _gen = 0  # the write generation: one more after every call that took this object over as its `into`, and after close()
 
     def __init__(self, eng: "Engine", handle):
         self.eng, self.h = eng, handle
+
+    def close(self):
+        self._gen += 1
+        _Owner.close(self)
 
     def info(self):
         ns, nv = C.c_uint64(), C.c_uint64()
@@ -536,7 +549,7 @@ class Compare(_Owner):
     Sets.compare_counted also dot[n_a, n_b] and min_sum[n_a, n_b] (u64)."""
 
     _release = "bsk_compare_release"
-    _whost = _norms = _operands = None  # the weighted side: (dot, min_sum); (sumsq_a, sumsq_b, totals_a, totals_b); the two Sets
+    _whost = _norms = _operands = _gens = None  # the weighted side: (dot, min_sum); (sumsq_a, sumsq_b, totals_a, totals_b); the two Sets; their generations at bind time
 
     def __init__(self, eng: "Engine"):
         self.eng, self.h = eng, None
@@ -546,6 +559,7 @@ class Compare(_Owner):
         self.h, self._host = h, None
         self.a_sizes = a_sizes.astype(np.uint64)
         self._whost, self._norms, self._operands = None, None, operands
+        self._gens = None if operands is None else tuple(x._gen for x in operands)
 
     def info(self):
         na, nb, lim = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -650,6 +664,7 @@ class Compare(_Owner):
             raise ValueError(what + " is defined on whole sets: compare_counted with limit=0")
         if self._norms is None:
             a, b = self._operands
+            _same_sets((a, b), self._gens, what)
             qa, ta = a.sumsq(), a.totals()
             qb, tb = (qa, ta) if b is a else (b.sumsq(), b.totals())
             self._norms = (qa, qb, ta, tb)
@@ -732,13 +747,20 @@ class Index(_Owner):
         """search() with the counts (bsk_index_search_counted): the same hits, bit for bit -- the thresholds read shared only -- and per
         hit .dot and .min_sum over the values both sets hold, as Sets.compare_counted defines them with limit 0.  Queries or an index
         without counts count 1 for every value.  The Hits are bound to the queries' sumsq() and totals() and the index's norms() -- fetched
-        when a formula first asks for them -- so cosine() and its kin work without the target sets; against an index without counts weighted_containment() is the share of
+        when a formula first asks for them, which raises ValueError once the queries were written or closed or this handle was closed -- so cosine() and its kin work without the target sets; against an index without counts weighted_containment() is the share of
         the query's mass found.  reuse: any Hits of this engine, whose device arrays are kept."""
         sp = L.SearchParams(min_shared, 0, min_query_cov, min_target_cov)
         h = _take_over(self.eng, reuse, lambda out: self.eng.lib.bsk_index_search_counted(self.eng.ctx, self.h, queries.h, C.byref(sp), out))
         res = reuse if reuse is not None else Hits(self.eng)
         res._bind(h, np.diff(queries.offsets()), self.target_sizes)
-        res._norm_source = lambda: (queries.sumsq(), self.norms()[0], queries.totals(), self.norms()[1])  # fetched when a formula first asks
+
+        def source():  # fetched when a formula first asks
+            if self._norms is None and not self.h:
+                raise ValueError("the index was closed since the call, before a formula fetched its norms")
+            return queries.sumsq(), self.norms()[0], queries.totals(), self.norms()[1]
+
+        res._norm_source = source
+        res._gens = ((queries,), (queries._gen,))  # (the index's own norms cannot change)
         res._plain_targets = not self.counted
         return res
 
@@ -759,6 +781,7 @@ class Hits(_Owner):
     _weights = _norms = _operands = None  # the weighted side (Sets.neighbors_counted): (dot, min_sum), fetched with the others; (sumsq_a, sumsq_b, totals_a, totals_b); (a, b, limit)
     _plain_targets = None  # Index.search_counted: whether the index kept no counts (weighted_containment() is defined there); None for any other hits
     _norm_source = None  # Index.search_counted: () -> (sumsq_q, sumsq_t, totals_q, totals_t), from the queries and the index's own norms
+    _gens = None  # (the Sets the norms will be fetched from, their generations at bind time): the norms are those of the call's operands
 
     def __init__(self, eng: "Engine"):
         self.eng, self.h = eng, None
@@ -767,6 +790,7 @@ class Hits(_Owner):
     def _bind(self, h, query_sizes: np.ndarray, target_sizes: np.ndarray, operands=None):
         self.h, self._host, self._totals, self._members = h, None, None, None
         self._weights, self._norms, self._operands, self._plain_targets, self._norm_source = None, None, operands, None, None
+        self._gens = None if operands is None else (operands[:2], tuple(x._gen for x in operands[:2]))
         self.query_sizes, self.target_sizes = query_sizes.astype(np.uint64), target_sizes
 
     def info(self):
@@ -980,6 +1004,8 @@ class Hits(_Owner):
         self._cache()
         if self._weights is None:
             raise ValueError("hits without weights: use Sets.neighbors_counted or Index.search_counted")
+        if self._norms is None and self._gens is not None:
+            _same_sets(*self._gens, what)
         if self._norms is None and self._norm_source is not None:
             self._norms = self._norm_source()
         if self._norms is None:
