@@ -84,6 +84,16 @@ class FoldParams(C.Structure):
     _fields_ = [("min_members", C.c_uint32), ("flags", C.c_uint32), ("frac_num", C.c_uint32), ("frac_den", C.c_uint32)]
 
 
+class Measure(C.Structure):
+    """bsk_measure (include/biosketch.h)"""
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("qnorm", C.c_void_p), ("n_qnorm", C.c_uint64), ("tnorm", C.c_void_p), ("n_tnorm", C.c_uint64)]
+
+
+class FilterParams(C.Structure):
+    """bsk_filter_params (include/biosketch.h)"""
+    _fields_ = [("min_num", C.c_uint64), ("min_den", C.c_uint64)]
+
+
 class SearchParams(C.Structure):
     """bsk_search_params (include/biosketch.h)"""
     _fields_ = [("min_shared", C.c_uint32), ("reserved", C.c_uint32), ("min_query_cov", C.c_double), ("min_target_cov", C.c_double)]
@@ -227,12 +237,16 @@ SYMBOLS = [
     ("bsk_hits_fold", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(FoldParams), _pp]),
     ("bsk_hits_members_device", C.c_int, [_vp, _pp]),
     ("bsk_hits_fetch_members", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64]),
+    ("bsk_hits_filter", C.c_int, [_vp, _vp, C.POINTER(Measure), C.POINTER(FilterParams), _pp]),
+    ("bsk_hits_top_by", C.c_int, [_vp, _vp, C.POINTER(Measure), C.c_uint32, _pp]),
     ("bsk_index_build_counted", C.c_int, [_vp, _vp, _pp]),
     ("bsk_index_counted", C.c_int, [_vp, C.POINTER(C.c_int)]),
     ("bsk_index_fetch_norms", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
     ("bsk_index_search_counted", C.c_int, [_vp, _vp, _vp, C.POINTER(SearchParams), _pp]),
 ]
 WINDOWS_COUNTED = 1
+(MEASURE_SHARED, MEASURE_MEMBERS, MEASURE_DOT, MEASURE_MIN_SUM, MEASURE_QUERY_COV, MEASURE_TARGET_COV, MEASURE_JACCARD, MEASURE_COSINE, MEASURE_WEIGHTED_JACCARD,
+ MEASURE_BC_SIMILARITY, MEASURE_QUERY_MASS) = range(11)
 NEIGHBORS_UPPER = 1
 CLUSTER_COMPONENTS, CLUSTER_GREEDY = 0, 1
 SETS_PER_SEQUENCE, SETS_WHOLE_BATCH = 0, 1

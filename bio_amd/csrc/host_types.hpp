@@ -78,7 +78,9 @@ enum PoolSlot {
     SLOT_FOLD_MAP = 54, SLOT_FOLD_WORK = 55,
     // weighted containment search (search.hip): the payload pass's chunk offsets, scan parts and figures; the saturation bits of its hits
     SLOT_SW_QUERY = 56, SLOT_SW_FLAGS = 57,
-    POOL_SLOTS = 58
+    // hits selected by a measure (select.hip): figures, flags and scans; the norms of the call; the global sort path's hit indices
+    SLOT_SELECT_WORK = 58, SLOT_SELECT_NORMS = 59, SLOT_SELECT_INDEX = 60,
+    POOL_SLOTS = 61
 };
 
 struct bsk_ctx {

@@ -409,6 +409,14 @@ class SearchHits : public Owned<bsk_hits, bsk_hits_release> {
         if (group_offsets.empty()) return BSK_ERR_ARG;
         return bsk_hits_fold(e.ctx(), p_, group_offsets.data(), group_offsets.size() - 1, fp, &into.handle());
     }
+    // the hits whose measure m is at least min_num / min_den, compared exactly (bsk_hits_filter): rows in their order, every payload kept;
+    // m.qnorm / m.tnorm are host arrays, read during the call only; into: empty, or any hits of this engine but this object
+    int filter(Engine &e, const bsk_measure &m, uint64_t min_num, uint64_t min_den, SearchHits &into) const {
+        const bsk_filter_params fp{min_num, min_den};
+        return bsk_hits_filter(e.ctx(), p_, &m, &fp, &into.handle());
+    }
+    // every query's min(n, hits) hits of largest measure, best first, ties by ascending target, every payload kept (bsk_hits_top_by)
+    int top_by(Engine &e, const bsk_measure &m, uint32_t n, SearchHits &into) const { return bsk_hits_top_by(e.ctx(), p_, &m, n, &into.handle()); }
     const uint32_t *members_device() const {  // nullptr for hits without members
         const uint32_t *m = nullptr;
         bsk_hits_members_device(p_, &m);

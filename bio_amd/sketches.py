@@ -24,6 +24,7 @@ or CPU implementation here.
 from __future__ import annotations
 
 import ctypes as C
+import fractions
 import math
 import os
 from typing import Iterable, List, Optional, Sequence, Tuple
@@ -828,6 +829,94 @@ class Hits(_Owner):
         res._bind(h, self.query_sizes, np.diff(go))
         return res
 
+    # -- selection by a measure (bsk_hits_filter, bsk_hits_top_by): every payload stays with its hit
+    _MEASURES = {  # name -> (kind, which norms: None, "sizes", "sumsq", "totals"; which sides)
+        "shared": (L.MEASURE_SHARED, None, ""), "members": (L.MEASURE_MEMBERS, None, ""), "dot": (L.MEASURE_DOT, None, ""), "min_sum": (L.MEASURE_MIN_SUM, None, ""),
+        "query_cov": (L.MEASURE_QUERY_COV, "sizes", "q"), "target_cov": (L.MEASURE_TARGET_COV, "sizes", "t"), "jaccard": (L.MEASURE_JACCARD, "sizes", "qt"),
+        "cosine": (L.MEASURE_COSINE, "sumsq", "qt"), "weighted_jaccard": (L.MEASURE_WEIGHTED_JACCARD, "totals", "qt"),
+        "bray_curtis_similarity": (L.MEASURE_BC_SIMILARITY, "totals", "qt"), "weighted_containment": (L.MEASURE_QUERY_MASS, "totals", "q"),
+    }
+
+    def _measure(self, measure: str, qnorm, tnorm):
+        """-> (L.Measure, the arrays it points into): the norms given, or those the formula of the same name would take"""
+        if measure not in self._MEASURES:
+            raise ValueError("measure: one of " + ", ".join(self._MEASURES))
+        kind, norms, sides = self._MEASURES[measure]
+        if measure == "jaccard" and self.has_totals():
+            sides = ""  # shared / total: no norms
+        if measure == "weighted_containment" and qnorm is None:
+            if self._plain_targets is None:
+                raise ValueError("weighted_containment is defined on the hits of Index.search_counted")
+            if not self._plain_targets:
+                raise ValueError("weighted_containment is defined against an index without counts (Sets.index): dot against a counted index is a product")
+        q = t = None
+        if "q" in sides:
+            q = qnorm if qnorm is not None else self.query_sizes if norms == "sizes" else self._norm_arrays(measure)[0 if norms == "sumsq" else 2]
+        if "t" in sides:
+            t = tnorm if tnorm is not None else self.target_sizes if norms == "sizes" else self._norm_arrays(measure)[1 if norms == "sumsq" else 3]
+        q = None if q is None else np.ascontiguousarray(q, np.uint64)
+        t = None if t is None else np.ascontiguousarray(t, np.uint64)
+        keep = [x if x is None or x.size else np.zeros(1, np.uint64) for x in (q, t)]  # (an empty array still has an address)
+        m = L.Measure(kind, 0, None if q is None else keep[0].ctypes.data, 0 if q is None else q.size, None if t is None else keep[1].ctypes.data,
+                      0 if t is None else t.size)
+        return m, keep
+
+    @staticmethod
+    def _at_least(at_least):
+        """-> (num, den) u64: an int, a fractions.Fraction, a (num, den) pair, or a float taken exactly"""
+        if isinstance(at_least, tuple):
+            num, den = int(at_least[0]), int(at_least[1])
+        elif isinstance(at_least, fractions.Fraction):
+            num, den = at_least.numerator, at_least.denominator
+        elif isinstance(at_least, (int, np.integer)):
+            num, den = int(at_least), 1
+        else:
+            x = float(at_least)
+            if x != x or x in (float("inf"), float("-inf")):
+                raise ValueError("at_least: not a finite number")
+            num, den = x.as_integer_ratio()
+        if den < 0:
+            num, den = -num, -den
+        if den == 0:
+            raise ValueError("at_least: denominator 0")
+        if num < 0:
+            num, den = 0, 1  # (no measure is negative)
+        if num >= 1 << 64 or den >= 1 << 64:
+            raise ValueError("at_least: numerator or denominator beyond 64 bits; give a fractions.Fraction with smaller parts")
+        return num, den
+
+    def _selected(self, h, reuse: Optional["Hits"]) -> "Hits":
+        """the Hits around a selection of self: the sizes, and the norms -- the snapshot if one was taken, else the way to take it"""
+        res = reuse if reuse is not None else Hits(self.eng)
+        carry = (self._norms, self._operands, self._gens, self._norm_source, self._plain_targets)
+        res._bind(h, self.query_sizes, self.target_sizes)
+        res._norms, res._operands, res._gens, res._norm_source, res._plain_targets = carry
+        return res
+
+    def filter(self, measure: str, at_least, *, qnorm=None, tnorm=None, reuse: Optional["Hits"] = None) -> "Hits":
+        """The hits whose measure is at least `at_least`, rows in their order, every payload kept (bsk_hits_filter) -> Hits.
+        measure: "shared", "members", "dot", "min_sum", "query_cov", "target_cov", "jaccard", "cosine", "weighted_jaccard",
+        "bray_curtis_similarity" (1 - bray_curtis()) or "weighted_containment".  at_least: an int, a fractions.Fraction, a (num, den)
+        pair or a float, which is taken exactly (float.as_integer_ratio); the comparison is in integers, no rounding.  The norms are
+        those the formula of the same name takes -- the sizes, or the operands' sumsq() / totals() under the rule of cosine() --
+        unless qnorm / tnorm give them (u64 per query / per target).  The result keeps the norms: its formulas work without the
+        operands.  reuse: any Hits of this engine, but not self."""
+        m, keep = self._measure(measure, qnorm, tnorm)
+        num, den = self._at_least(at_least)
+        fp = L.FilterParams(num, den)
+        h = _take_over(self.eng, reuse, lambda out: self.eng.lib.bsk_hits_filter(self.eng.ctx, self.h, C.byref(m), C.byref(fp), out))
+        del keep
+        return self._selected(h, reuse)
+
+    def top_by(self, n: int, measure: str, *, qnorm=None, tnorm=None, reuse: Optional["Hits"] = None) -> "Hits":
+        """Every query's min(n, hits) hits of largest measure, best first, ties by ascending target, every payload kept
+        (bsk_hits_top_by) -> Hits.  measure and norms as in filter(); with "shared" the hits are those of top(n), which drops the
+        payloads.  reuse: any Hits of this engine, but not self."""
+        m, keep = self._measure(measure, qnorm, tnorm)
+        h = _take_over(self.eng, reuse, lambda out: self.eng.lib.bsk_hits_top_by(self.eng.ctx, self.h, C.byref(m), n, out))
+        del keep
+        return self._selected(h, reuse)
+
     def has_members(self) -> bool:
         """whether the last entry that wrote these hits kept members (bsk_hits_members_device gives an array): fold() does"""
         if not self.h:
@@ -998,24 +1087,31 @@ class Hits(_Owner):
 
 
     # -- the weighted side (bsk_sets_neighbors_counted): Compare's formulas, per hit
-    def _whole(self, what: str):
-        """(dot, min_sum, sumsq_a, sumsq_b, totals_a, totals_b) per hit of weighted hits over whole sets: the norms of the two operands
-        gathered by query() and target"""
-        self._cache()
-        if self._weights is None:
-            raise ValueError("hits without weights: use Sets.neighbors_counted or Index.search_counted")
+    def _norm_arrays(self, what: str):
+        """(sumsq_a, sumsq_b, totals_a, totals_b) of the operands as the call that made the hits saw them: kept once fetched, fetched
+        only while the operands are unwritten"""
         if self._norms is None and self._gens is not None:
             _same_sets(*self._gens, what)
         if self._norms is None and self._norm_source is not None:
             self._norms = self._norm_source()
         if self._norms is None:
+            if self._operands is None:
+                raise ValueError(what + ": these hits know no operands to take norms from; pass qnorm= and tnorm=")
             a, b, limit = self._operands
             if limit != 0:
                 raise ValueError(what + " is defined on whole sets: neighbors_counted with limit=0")
             qa, ta = a.sumsq(), a.totals()
             qb, tb = (qa, ta) if b is a else (b.sumsq(), b.totals())
             self._norms = (qa, qb, ta, tb)
-        qa, qb, ta, tb = self._norms
+        return self._norms
+
+    def _whole(self, what: str):
+        """(dot, min_sum, sumsq_a, sumsq_b, totals_a, totals_b) per hit of weighted hits over whole sets: the norms of the two operands
+        gathered by query() and target"""
+        self._cache()
+        if self._weights is None:
+            raise ValueError("hits without weights: use Sets.neighbors_counted or Index.search_counted")
+        qa, qb, ta, tb = self._norm_arrays(what)
         i, j = self.query().astype(np.int64), self.target.astype(np.int64)
         return self._weights[0], self._weights[1], qa[i], qb[j], ta[i], tb[j]
 

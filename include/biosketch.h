@@ -497,6 +497,9 @@ int bsk_result_sets(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk
  *     BSK_ERR_DEVICE release.
  *   bsk_hits_fold: every BSK_ERR_ARG -- a row that is not strictly ascending and a target beyond the last group included, which one
  *     small device pass finds before the object is taken over -- and the 2^32 limits keep the slot; BSK_ERR_NOMEM and BSK_ERR_DEVICE release.
+ *   bsk_hits_filter, bsk_hits_top_by: every BSK_ERR_ARG -- a target beyond the target norms and a denominator that is not positive
+ *     included, which one small device pass finds before the object is taken over -- and the 2^32 limits keep the slot; BSK_ERR_NOMEM
+ *     and BSK_ERR_DEVICE release.
  *   bsk_result_sets_windows: as bsk_sets_compare -- every BSK_ERR_ARG keeps the slot; both 2^32 limits (BSK_ERR_UNSUPPORTED: the windows in
  *     total, the gathered tuples), known after a read-back, release it, as BSK_ERR_NOMEM and BSK_ERR_DEVICE do.
  *   bsk_result_sets_reuse, _counted: a NULL `sets` and sets of another context (BSK_ERR_ARG) keep the slot.  Every other error releases:
@@ -851,6 +854,59 @@ int bsk_hits_fold(bsk_ctx *ctx, const bsk_hits *h, const uint64_t *group_offsets
                   const bsk_fold_params *fp /* NULL: {1,0,0,0} */, bsk_hits **out);
 int bsk_hits_members_device(const bsk_hits *h, const uint32_t **members);  /* NULL for hits without members */
 int bsk_hits_fetch_members(bsk_ctx *ctx, const bsk_hits *h, uint64_t first, uint64_t count, uint32_t *members, uint64_t hit_cap);
+
+/* ---- hits selected by a measure: an exact filter, a top-n that keeps the payloads ----
+ * bsk_hits_filter keeps the hits whose measure reaches a threshold, bsk_hits_top_by keeps every row's n hits of largest measure.  Both
+ * carry every payload h carries -- total, dot / min_sum, members -- with the same has-flags, so thresholds on the weighted measures,
+ * the k nearest neighbours by cosine, the best genome of a fold with its members and clustering by a weighted measure
+ * (filter, then bsk_hits_cluster) all stay on the device.  bsk_hits_top itself is unchanged and still drops the payloads.
+ * The measure.  Every measure of hit i is an exact fraction N/D of non-negative integers.  The hit belongs to query q and has target t,
+ * Q = qnorm[q] and T = tnorm[t]:
+ *   BSK_MEASURE_SHARED            N = shared          D = 1
+ *   BSK_MEASURE_MEMBERS           N = members         D = 1                      needs hits with members
+ *   BSK_MEASURE_DOT               N = dot             D = 1                      needs weights
+ *   BSK_MEASURE_MIN_SUM           N = min_sum         D = 1                      needs weights
+ *   BSK_MEASURE_QUERY_COV         N = shared          D = Q                      qnorm: the queries' sizes
+ *   BSK_MEASURE_TARGET_COV        N = shared          D = T                      tnorm: the targets' sizes
+ *   BSK_MEASURE_JACCARD           N = shared          D = total[i] where h has totals, else Q + T - shared (both norms: sizes)
+ *   BSK_MEASURE_COSINE            N = dot * dot       D = Q * T                  weights, both norms: bsk_sets_sumsq
+ *   BSK_MEASURE_WEIGHTED_JACCARD  N = min_sum         D = Q + T - min_sum        weights, both norms: bsk_sets_totals
+ *   BSK_MEASURE_BC_SIMILARITY     N = 2 * min_sum     D = Q + T                  weights, both norms: bsk_sets_totals
+ *   BSK_MEASURE_QUERY_MASS        N = dot             D = Q                      weights, qnorm: bsk_sets_totals
+ * COSINE's N/D is the squared cosine -- the order is the cosine's, and the filter squares its bound to match.  BC_SIMILARITY is
+ * 1 - Bray-Curtis: "dissimilarity <= x" is "similarity >= 1 - x".  A saturated dot is the number 2^64-1, as everywhere else.  D is
+ * formed in more than 64 bits (Q + T overflows a u64); N, D and every product below fit 256 bits (wide_uint.hpp).  Integers only: no
+ * division, no rounding, no float.
+ * qnorm[n_qnorm] and tnorm[n_tnorm] are host arrays, not retained; NULL / 0 where the kind needs none (given anyway, they are ignored).
+ * BSK_ERR_ARG, all of which keep the slot: a NULL ctx, h, m or slot; an unknown kind; a flag bit; a payload or a norm the kind needs
+ * that is absent; n_qnorm != n_queries where qnorm is needed; *out == h; hits or *out of another context; and, found by one small device
+ * pass (k_sel_check) before the object is taken over, a hit with target >= n_tnorm where tnorm is needed and a hit with D <= 0 (norms
+ * inconsistent with the hits).  n_queries >= 2^32 or n_hits >= 2^32 is BSK_ERR_UNSUPPORTED and keeps the slot too; BSK_ERR_NOMEM and
+ * BSK_ERR_DEVICE release it.  The input need not have ascending rows: the output of bsk_hits_top / _top_by is legal input.
+ * bsk_hits_filter: a hit is kept iff N * min_den >= min_num * D; for COSINE iff N * min_den^2 >= min_num^2 * D, so the bound is on the
+ * cosine itself.  min_den == 0 is BSK_ERR_ARG.  Rows keep their order, offsets shrink.  How it runs: the flag pass fused with the check
+ * (k_sel_check), the library's scan, the new offsets read from the scan at the old offsets (k_sel_offsets) and one placement pass
+ * (k_sel_place).  No atomics on the output and no kernel that waits on another: the result is bit-identical from call to call.
+ * bsk_hits_plan names the kernels and reports kept= as a decimal figure; n_large_queries is 0.
+ * bsk_hits_top_by: per query the min(n, hits) hits of largest measure.  Hit a is better than hit b iff N_a * D_b > N_b * D_a, ties by
+ * ascending target (the targets of a row are distinct for everything the library produces); hits are stored best first, as
+ * bsk_hits_top stores them.  n == 0 is BSK_ERR_ARG.  With BSK_MEASURE_SHARED offsets, target and shared are bit-identical to
+ * bsk_hits_top(h, n).  How it runs: rows of at most 16 hits are ranked by a group of 16 lanes (k_tb_group); rows of at most 1 024 hits
+ * have their hit indices sorted by a wavefront in LDS on the bitonic network, with the comparator (k_tb_lds); longer rows take a
+ * workgroup each, which sorts a u32 index array in pooled global memory on the same network, __syncthreads() between the steps
+ * (k_tb_global: c log^2 c compares by ONE workgroup -- filter first where rows hold far more than 10^4 hits).  Every kernel gathers all
+ * arrays by the sorted indices.  bsk_hits_plan reports the queries per path; n_large_queries is the count of the global path. */
+enum { BSK_MEASURE_SHARED = 0, BSK_MEASURE_MEMBERS, BSK_MEASURE_DOT, BSK_MEASURE_MIN_SUM,
+       BSK_MEASURE_QUERY_COV, BSK_MEASURE_TARGET_COV, BSK_MEASURE_JACCARD,
+       BSK_MEASURE_COSINE, BSK_MEASURE_WEIGHTED_JACCARD, BSK_MEASURE_BC_SIMILARITY, BSK_MEASURE_QUERY_MASS };
+typedef struct bsk_measure {
+    uint32_t kind, flags;                      /* flags 0; any bit: BSK_ERR_ARG */
+    const uint64_t *qnorm; uint64_t n_qnorm;   /* host, not retained; NULL / 0 where the kind needs none */
+    const uint64_t *tnorm; uint64_t n_tnorm;
+} bsk_measure;
+typedef struct bsk_filter_params { uint64_t min_num, min_den; } bsk_filter_params;  /* min_den == 0: BSK_ERR_ARG */
+int bsk_hits_filter(bsk_ctx *ctx, const bsk_hits *h, const bsk_measure *m, const bsk_filter_params *fp, bsk_hits **out);
+int bsk_hits_top_by(bsk_ctx *ctx, const bsk_hits *h, const bsk_measure *m, uint32_t n, bsk_hits **top);
 
 /* ---- clusters of a neighbour graph: connected components and greedy representatives ----
  * (bsk_sets_neighbors, which makes such a graph from sets, is declared below this block: it closes the header.)
