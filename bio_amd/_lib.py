@@ -239,12 +239,20 @@ SYMBOLS = [
     ("bsk_hits_fetch_members", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64]),
     ("bsk_hits_filter", C.c_int, [_vp, _vp, C.POINTER(Measure), C.POINTER(FilterParams), _pp]),
     ("bsk_hits_top_by", C.c_int, [_vp, _vp, C.POINTER(Measure), C.c_uint32, _pp]),
+    ("bsk_hits_transpose", C.c_int, [_vp, _vp, C.c_uint64, _pp]),
+    ("bsk_hits_tally", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _pp]),
+    ("bsk_tally_info", C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p]),
+    ("bsk_tally_plan", C.c_int, [_vp, C.POINTER(C.c_char_p)]),
+    ("bsk_tally_fetch", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
+    ("bsk_tally_device", C.c_int, [_vp, _pp, _pp, _pp]),
+    ("bsk_tally_release", None, [_vp]),
     ("bsk_index_build_counted", C.c_int, [_vp, _vp, _pp]),
     ("bsk_index_counted", C.c_int, [_vp, C.POINTER(C.c_int)]),
     ("bsk_index_fetch_norms", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
     ("bsk_index_search_counted", C.c_int, [_vp, _vp, _vp, C.POINTER(SearchParams), _pp]),
 ]
 WINDOWS_COUNTED = 1
+TALLY_ADD = 1
 (MEASURE_SHARED, MEASURE_MEMBERS, MEASURE_DOT, MEASURE_MIN_SUM, MEASURE_QUERY_COV, MEASURE_TARGET_COV, MEASURE_JACCARD, MEASURE_COSINE, MEASURE_WEIGHTED_JACCARD,
  MEASURE_BC_SIMILARITY, MEASURE_QUERY_MASS) = range(11)
 NEIGHBORS_UPPER = 1

@@ -80,7 +80,9 @@ enum PoolSlot {
     SLOT_SW_QUERY = 56, SLOT_SW_FLAGS = 57,
     // hits selected by a measure (select.hip): figures, flags and scans; the norms of the call; the global sort path's hit indices
     SLOT_SELECT_WORK = 58, SLOT_SELECT_NORMS = 59, SLOT_SELECT_INDEX = 60,
-    POOL_SLOTS = 61
+    // hits by target (transpose.hip): the transpose's figure, sort keys and sort storage; the tally's figure
+    SLOT_TRANSPOSE_WORK = 61, SLOT_TALLY_WORK = 62,
+    POOL_SLOTS = 63
 };
 
 struct bsk_ctx {

@@ -358,6 +358,40 @@ class Clusters : public Owned<bsk_clusters, bsk_clusters_release> {
     }
 };
 
+// the per-target table of hits (bsk_tally): rows[n_targets], unique[n_targets], shared[n_targets], u64 each
+class Tally : public Owned<bsk_tally, bsk_tally_release> {
+   public:
+    uint64_t n_targets() const { return info(0); }
+    // what the table holds: the rows, hits and calls tallied into it (they add up under BSK_TALLY_ADD)
+    uint64_t queries() const { return info(1); }
+    uint64_t hits() const { return info(2); }
+    uint64_t calls() const { return info(3); }
+    std::string plan() const {
+        const char *p = "";
+        bsk_tally_plan(p_, &p);
+        return p ? p : "";
+    }
+    int fetch(Engine &e, std::vector<uint64_t> &rows, std::vector<uint64_t> &unique, std::vector<uint64_t> &shared) const {
+        const uint64_t n = n_targets();
+        rows.assign(n + 1, 0);
+        unique.assign(n + 1, 0);
+        shared.assign(n + 1, 0);
+        const int rc = bsk_tally_fetch(e.ctx(), p_, 0, n, rows.data(), unique.data(), shared.data());
+        rows.resize(n);
+        unique.resize(n);
+        shared.resize(n);
+        return rc;
+    }
+    void device(const uint64_t *&rows, const uint64_t *&unique, const uint64_t *&shared) const { bsk_tally_device(p_, &rows, &unique, &shared); }
+
+   private:
+    uint64_t info(int i) const {
+        uint64_t v[4] = {0, 0, 0, 0};
+        bsk_tally_info(p_, &v[0], &v[1], &v[2], &v[3]);
+        return v[i];
+    }
+};
+
 // hits of a search (bsk_hits): CSR by query, target ids ascending inside a query
 class SearchHits : public Owned<bsk_hits, bsk_hits_release> {
    public:
@@ -417,6 +451,14 @@ class SearchHits : public Owned<bsk_hits, bsk_hits_release> {
     }
     // every query's min(n, hits) hits of largest measure, best first, ties by ascending target, every payload kept (bsk_hits_top_by)
     int top_by(Engine &e, const bsk_measure &m, uint32_t n, SearchHits &into) const { return bsk_hits_top_by(e.ctx(), p_, &m, n, &into.handle()); }
+    // the hits by target (bsk_hits_transpose): n_targets rows, row t the queries that hit t, ascending, every payload with its hit; into:
+    // empty, or any hits of this engine but this object
+    int transpose(Engine &e, uint64_t n_targets, SearchHits &into) const { return bsk_hits_transpose(e.ctx(), p_, n_targets, &into.handle()); }
+    // the per-target table (bsk_hits_tally): into: empty, or an earlier table of this engine -- overwritten, or with add == true (and the
+    // same n_targets) added to
+    int tally(Engine &e, uint64_t n_targets, bool add, Tally &into) const {
+        return bsk_hits_tally(e.ctx(), p_, n_targets, add ? (uint32_t)BSK_TALLY_ADD : 0u, &into.handle());
+    }
     const uint32_t *members_device() const {  // nullptr for hits without members
         const uint32_t *m = nullptr;
         bsk_hits_members_device(p_, &m);

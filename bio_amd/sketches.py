@@ -783,6 +783,7 @@ class Hits(_Owner):
     _plain_targets = None  # Index.search_counted: whether the index kept no counts (weighted_containment() is defined there); None for any other hits
     _norm_source = None  # Index.search_counted: () -> (sumsq_q, sumsq_t, totals_q, totals_t), from the queries and the index's own norms
     _gens = None  # (the Sets the norms will be fetched from, their generations at bind time): the norms are those of the call's operands
+    _flip = None  # transpose(): (the _plain_targets of the hits this object is the transpose of,); None for hits in their own orientation
 
     def __init__(self, eng: "Engine"):
         self.eng, self.h = eng, None
@@ -790,7 +791,7 @@ class Hits(_Owner):
 
     def _bind(self, h, query_sizes: np.ndarray, target_sizes: np.ndarray, operands=None):
         self.h, self._host, self._totals, self._members = h, None, None, None
-        self._weights, self._norms, self._operands, self._plain_targets, self._norm_source = None, None, operands, None, None
+        self._weights, self._norms, self._operands, self._plain_targets, self._norm_source, self._flip = None, None, operands, None, None, None
         self._gens = None if operands is None else (operands[:2], tuple(x._gen for x in operands[:2]))
         self.query_sizes, self.target_sizes = query_sizes.astype(np.uint64), target_sizes
 
@@ -888,9 +889,46 @@ class Hits(_Owner):
     def _selected(self, h, reuse: Optional["Hits"]) -> "Hits":
         """the Hits around a selection of self: the sizes, and the norms -- the snapshot if one was taken, else the way to take it"""
         res = reuse if reuse is not None else Hits(self.eng)
-        carry = (self._norms, self._operands, self._gens, self._norm_source, self._plain_targets)
+        carry = (self._norms, self._operands, self._gens, self._norm_source, self._plain_targets, self._flip)
         res._bind(h, self.query_sizes, self.target_sizes)
-        res._norms, res._operands, res._gens, res._norm_source, res._plain_targets = carry
+        res._norms, res._operands, res._gens, res._norm_source, res._plain_targets, res._flip = carry
+        return res
+
+    # -- hits by target (bsk_hits_transpose, bsk_hits_tally)
+    def _n_targets(self, n_targets) -> int:
+        return len(self.target_sizes) if n_targets is None else int(n_targets)
+
+    def transpose(self, n_targets: Optional[int] = None, reuse: Optional["Hits"] = None) -> "Hits":
+        """The hits by target (bsk_hits_transpose) -> Hits of n_targets rows (default: len(target_sizes)): row t lists the queries that hit
+        t, ascending, every payload with its hit.  The result is bound with the sizes swapped, and so are the norms of the weighted
+        side: jaccard(), containment(), cosine(), weighted_jaccard(), bray_curtis() and filter / top_by with their default norms read
+        it as the hits of the targets against the queries.  weighted_containment(), which is one-sided, raises on it.  reuse: any Hits
+        of this engine, but not self."""
+        nt = self._n_targets(n_targets)
+        h = _take_over(self.eng, reuse, lambda out: self.eng.lib.bsk_hits_transpose(self.eng.ctx, self.h, nt, out))
+        res = reuse if reuse is not None else Hits(self.eng)
+        norms, operands, gens, source = self._norms, self._operands, self._gens, self._norm_source
+        plain, flip = self._plain_targets, self._flip
+        rows = np.zeros(nt, np.uint64)  # (targets beyond the sizes known here are rows of size 0: nobody hit them)
+        known = np.asarray(self.target_sizes, np.uint64)[:nt]
+        rows[:len(known)] = known
+        res._bind(h, rows, self.query_sizes)
+        swap = lambda n: (n[1], n[0], n[3], n[2])  # noqa: E731
+        if norms is not None:
+            res._norms = swap(norms)
+        else:
+            res._norm_source = lambda: swap(Hits._resolve_norms(operands, gens, source, "a formula of transposed hits"))
+        res._plain_targets, res._flip = (flip[0], None) if flip is not None else (None, (plain,))
+        return res
+
+    def tally(self, n_targets: Optional[int] = None, into: Optional["Tally"] = None, add: bool = False) -> "Tally":
+        """The per-target table of the hits (bsk_hits_tally) -> Tally: .rows[t] the hits that name t, .unique[t] those that are the only
+        hit of their row, .shared[t] the sum of their shared.  n_targets: default len(target_sizes).  into: the Tally of an earlier
+        call on this engine, overwritten -- or, with add=True, added to (a table of the same n_targets; its info() adds up too)."""
+        nt = self._n_targets(n_targets)
+        h = _take_over(self.eng, into, lambda out: self.eng.lib.bsk_hits_tally(self.eng.ctx, self.h, nt, L.TALLY_ADD if add else 0, out))
+        res = into if into is not None else Tally(self.eng)
+        res._bind(h)
         return res
 
     def filter(self, measure: str, at_least, *, qnorm=None, tnorm=None, reuse: Optional["Hits"] = None) -> "Hits":
@@ -1090,20 +1128,25 @@ class Hits(_Owner):
     def _norm_arrays(self, what: str):
         """(sumsq_a, sumsq_b, totals_a, totals_b) of the operands as the call that made the hits saw them: kept once fetched, fetched
         only while the operands are unwritten"""
-        if self._norms is None and self._gens is not None:
-            _same_sets(*self._gens, what)
-        if self._norms is None and self._norm_source is not None:
-            self._norms = self._norm_source()
         if self._norms is None:
-            if self._operands is None:
-                raise ValueError(what + ": these hits know no operands to take norms from; pass qnorm= and tnorm=")
-            a, b, limit = self._operands
-            if limit != 0:
-                raise ValueError(what + " is defined on whole sets: neighbors_counted with limit=0")
-            qa, ta = a.sumsq(), a.totals()
-            qb, tb = (qa, ta) if b is a else (b.sumsq(), b.totals())
-            self._norms = (qa, qb, ta, tb)
+            self._norms = Hits._resolve_norms(self._operands, self._gens, self._norm_source, what)
         return self._norms
+
+    @staticmethod
+    def _resolve_norms(operands, gens, source, what: str):
+        """the norms from what a Hits knows of its operands (transpose() hands these on without the Hits itself)"""
+        if gens is not None:
+            _same_sets(*gens, what)
+        if source is not None:
+            return source()
+        if operands is None:
+            raise ValueError(what + ": these hits know no operands to take norms from; pass qnorm= and tnorm=")
+        a, b, limit = operands
+        if limit != 0:
+            raise ValueError(what + " is defined on whole sets: neighbors_counted with limit=0")
+        qa, ta = a.sumsq(), a.totals()
+        qb, tb = (qa, ta) if b is a else (b.sumsq(), b.totals())
+        return (qa, qb, ta, tb)
 
     def _whole(self, what: str):
         """(dot, min_sum, sumsq_a, sumsq_b, totals_a, totals_b) per hit of weighted hits over whole sets: the norms of the two operands
@@ -1148,6 +1191,8 @@ class Hits(_Owner):
         """per hit dot / totals_q[i]: the share of the query's mass -- the sum of its counts -- that lies on values the target holds
         (sourmash's abundance-weighted containment).  Defined for Index.search_counted against an index WITHOUT counts, where dot is
         the sum of the query's counts over the shared values; any other hits raise.  NaN where dot is saturated."""
+        if self._flip is not None:
+            raise ValueError("weighted_containment is one-sided (the share of the QUERY's mass): not defined on transposed hits; ask the hits before transpose()")
         if self._plain_targets is None:
             raise ValueError("weighted_containment is defined on the hits of Index.search_counted")
         if not self._plain_targets:
@@ -1156,6 +1201,64 @@ class Hits(_Owner):
         out = np.divide(dt.astype(np.float64), ta.astype(np.float64), out=np.zeros(dt.shape, np.float64), where=ta != 0)
         out[dt == int(np.iinfo(np.uint64).max)] = np.nan
         return out
+
+
+class Tally(_Owner):
+    """The per-target table of hits (bsk_tally): rows[n_targets], unique[n_targets], shared[n_targets], u64 each; fetched on first use."""
+
+    _release = "bsk_tally_release"
+
+    def __init__(self, eng: "Engine"):
+        self.eng, self.h = eng, None
+        self._host = None
+
+    def _bind(self, h):
+        self.h, self._host = h, None
+
+    def info(self):
+        v = [C.c_uint64() for _ in range(4)]
+        self.eng._chk(self.eng.lib.bsk_tally_info(self.h, *[C.byref(x) for x in v]))
+        return dict(n_targets=v[0].value, queries=v[1].value, hits=v[2].value, calls=v[3].value)
+
+    def plan(self) -> str:
+        """What the last call ran (bsk_tally_plan): the path -- counters in LDS or adds to the table -- with targets= and hits=."""
+        p = C.c_char_p()
+        self.eng._chk(self.eng.lib.bsk_tally_plan(self.h, C.byref(p)))
+        return (p.value or b"").decode()
+
+    def fetch(self, first: int = 0, count: Optional[int] = None):
+        """bsk_tally_fetch -> (rows[count], unique[count], shared[count]) of targets first .. first + count - 1"""
+        if count is None:
+            count = self.info()["n_targets"] - first
+        out = [np.zeros(max(count, 1), np.uint64) for _ in range(3)]
+        self.eng._chk(self.eng.lib.bsk_tally_fetch(self.eng.ctx, self.h, first, count, *[x.ctypes.data for x in out]))
+        return tuple(x[:count] for x in out)
+
+    def device(self):
+        """bsk_tally_device -> (rows_ptr, unique_ptr, shared_ptr)"""
+        p = [C.c_void_p() for _ in range(3)]
+        self.eng._chk(self.eng.lib.bsk_tally_device(self.h, *[C.byref(x) for x in p]))
+        return tuple(x.value for x in p)
+
+    def _cache(self):
+        if self._host is None:
+            self._host = self.fetch()
+        return self._host
+
+    @property
+    def rows(self) -> np.ndarray:
+        """per target the hits that name it"""
+        return self._cache()[0]
+
+    @property
+    def unique(self) -> np.ndarray:
+        """per target the hits that name it and are the only hit of their row"""
+        return self._cache()[1]
+
+    @property
+    def shared(self) -> np.ndarray:
+        """per target the sum of shared over the hits that name it"""
+        return self._cache()[2]
 
 
 class Clusters(_Owner):

@@ -500,6 +500,9 @@ int bsk_result_sets(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk
  *   bsk_hits_filter, bsk_hits_top_by: every BSK_ERR_ARG -- a target beyond the target norms and a denominator that is not positive
  *     included, which one small device pass finds before the object is taken over -- and the 2^32 limits keep the slot; BSK_ERR_NOMEM
  *     and BSK_ERR_DEVICE release.
+ *   bsk_hits_transpose, bsk_hits_tally (bsk_tally **out): every BSK_ERR_ARG -- a target >= n_targets included, which one small device
+ *     pass finds before the object is taken over, and for the tally a flag bit and a table of another n_targets -- and the 2^32 limits
+ *     keep the slot; BSK_ERR_NOMEM and BSK_ERR_DEVICE release.
  *   bsk_result_sets_windows: as bsk_sets_compare -- every BSK_ERR_ARG keeps the slot; both 2^32 limits (BSK_ERR_UNSUPPORTED: the windows in
  *     total, the gathered tuples), known after a read-back, release it, as BSK_ERR_NOMEM and BSK_ERR_DEVICE do.
  *   bsk_result_sets_reuse, _counted: a NULL `sets` and sets of another context (BSK_ERR_ARG) keep the slot.  Every other error releases:
@@ -907,6 +910,57 @@ typedef struct bsk_measure {
 typedef struct bsk_filter_params { uint64_t min_num, min_den; } bsk_filter_params;  /* min_den == 0: BSK_ERR_ARG */
 int bsk_hits_filter(bsk_ctx *ctx, const bsk_hits *h, const bsk_measure *m, const bsk_filter_params *fp, bsk_hits **out);
 int bsk_hits_top_by(bsk_ctx *ctx, const bsk_hits *h, const bsk_measure *m, uint32_t n, bsk_hits **top);
+
+/* ---- hits by target: the transpose with its payloads, the per-target tally ----
+ * Every result of the sets side is a bsk_hits, a CSR by query.  bsk_hits_transpose turns the table round -- which queries hit target t,
+ * a target's best query (transpose, then bsk_hits_top_by), reciprocal best hits -- and bsk_hits_tally is the one reduction everybody
+ * computes from it: how many hits went to each target and how many of them to that target alone (the table kmcp profile, a Kraken
+ * report and mash screen end in).  Neither chooses a policy; both compose with everything that takes hits.
+ *
+ * bsk_hits_transpose: the output has n_targets rows.  Row t lists, as its target[], the queries q of h that hit t, ascending; should a
+ * row of h name t twice (nothing the library produces does), those hits keep their order in h.  shared goes with its hit, and so does
+ * every payload h carries -- total, dot / min_sum, members -- with the same has-flags; a re-used *out of any history ends with exactly
+ * the flags of h.  Targets nobody hit are empty rows, trailing ones included: n_targets may exceed the largest target + 1.  The input
+ * need not have ascending rows: the output of bsk_hits_top / _top_by is legal input.  For an input with ascending rows
+ * transpose(transpose(h, n_targets), n_queries) is h, bit for bit, every array included.
+ * BSK_ERR_ARG, all of which keep the slot: a NULL ctx, h or out; *out == h; h or *out of another context; and, found by one small
+ * device pass (k_tp_keys) before the object is taken over, a hit with target >= n_targets.  n_targets, n_queries or n_hits of 2^32 or
+ * more is BSK_ERR_UNSUPPORTED and keeps the slot too; BSK_ERR_NOMEM and BSK_ERR_DEVICE release it.  n_hits == 0, n_queries == 0 and
+ * n_targets == 0 (without hits) give empty results with BSK_OK.
+ * How it runs: a key (target << hit_bits) | hit index per hit (k_tp_keys), every key distinct; the library's key sort over the
+ * key_bits = hit_bits + target_bits that matter; the output offsets by a search of every target's first key (k_tp_offsets); one
+ * placement pass that gathers every array by the sorted index and finds the hit's query by a search of h's offsets (k_tp_place).  No
+ * atomics on the output, no row of either side walked by one lane, nothing rests on the sort being stable: the result is a function
+ * of h and n_targets alone, bit-identical from call to call.  bsk_hits_plan names the kernels and reports targets=, hits= and
+ * key_bits= as decimal figures; n_large_queries is 0.
+ *
+ * bsk_hits_tally: per target t three u64 -- rows[t], the hits of h that name t; unique[t], those among them that are the only hit of
+ * their row; shared[t], the sum of their shared.  The sum is exact: 2^32 hits of 2^32 cannot reach 2^64 in one call; across
+ * BSK_TALLY_ADD calls the three arrays add modulo 2^64.  Weights, totals and members are not tallied: they are one bsk_hits_transpose
+ * away for whoever wants them.
+ * Without BSK_TALLY_ADD the table is that of h; a re-used object is overwritten, its arrays are kept and only grow.  With
+ * BSK_TALLY_ADD the figures of h are added to those *out holds, and queries, hits and calls of bsk_tally_info add up too; a NULL slot
+ * under ADD is a fresh table, a table of another n_targets is BSK_ERR_ARG.
+ * BSK_ERR_ARG / BSK_ERR_UNSUPPORTED: those of bsk_hits_transpose, and any other flag bit.  All of them keep the slot, and under ADD
+ * the table is unchanged: the target check (k_tl_check) runs, and its answer is read, before anything is added.
+ * How it runs: up to 2 048 targets a workgroup of 512 lanes adds into three u64 counters per target in LDS and then adds its non-zero
+ * counters to the table, one global add per counter and workgroup (3 x 8 B x 2 048 = 48 KB of a CU's 160 KB: three workgroups, six
+ * wavefronts per SIMD); beyond that the adds go straight to the table in global memory.  On both paths a wavefront whose hits all
+ * name one target sums on its lanes and adds once.  unique is found per row (offsets difference 1), rows and shared per hit.  The
+ * sums are integer adds: bit-identical from call to call.  bsk_tally_plan says which path ran and reports targets= and hits=.
+ * bsk_tally_info: n_targets, and the queries, hits and calls the table holds.  bsk_tally_fetch copies targets first .. first + count - 1
+ * of the arrays asked for (any pointer may be NULL); first + count > n_targets and a table of another context are BSK_ERR_ARG.
+ * bsk_tally_device: the device arrays, n_targets u64 each. */
+enum { BSK_TALLY_ADD = 1 };
+typedef struct bsk_tally bsk_tally;
+int bsk_hits_transpose(bsk_ctx *ctx, const bsk_hits *h, uint64_t n_targets, bsk_hits **out);
+int bsk_hits_tally(bsk_ctx *ctx, const bsk_hits *h, uint64_t n_targets, uint32_t flags, bsk_tally **out);
+int bsk_tally_info(const bsk_tally *t, uint64_t *n_targets, uint64_t *queries, uint64_t *hits, uint64_t *calls);
+int bsk_tally_plan(const bsk_tally *t, const char **plan);
+int bsk_tally_fetch(bsk_ctx *ctx, const bsk_tally *t, uint64_t first, uint64_t count,
+                    uint64_t *rows, uint64_t *unique, uint64_t *shared);   /* any may be NULL */
+int bsk_tally_device(const bsk_tally *t, const uint64_t **rows, const uint64_t **unique, const uint64_t **shared);
+void bsk_tally_release(bsk_tally *t);
 
 /* ---- clusters of a neighbour graph: connected components and greedy representatives ----
  * (bsk_sets_neighbors, which makes such a graph from sets, is declared below this block: it closes the header.)
