@@ -246,6 +246,7 @@ SYMBOLS = [
     ("bsk_tally_fetch", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     ("bsk_tally_device", C.c_int, [_vp, _pp, _pp, _pp]),
     ("bsk_tally_release", None, [_vp]),
+    ("bsk_hits_merge", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _pp]),
     ("bsk_index_build_counted", C.c_int, [_vp, _vp, _pp]),
     ("bsk_index_counted", C.c_int, [_vp, C.POINTER(C.c_int)]),
     ("bsk_index_fetch_norms", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
@@ -253,6 +254,8 @@ SYMBOLS = [
 ]
 WINDOWS_COUNTED = 1
 TALLY_ADD = 1
+MERGE_ADD = 1
+MERGE_MAX_PARTS = 64
 (MEASURE_SHARED, MEASURE_MEMBERS, MEASURE_DOT, MEASURE_MIN_SUM, MEASURE_QUERY_COV, MEASURE_TARGET_COV, MEASURE_JACCARD, MEASURE_COSINE, MEASURE_WEIGHTED_JACCARD,
  MEASURE_BC_SIMILARITY, MEASURE_QUERY_MASS) = range(11)
 NEIGHBORS_UPPER = 1

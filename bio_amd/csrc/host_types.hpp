@@ -82,7 +82,10 @@ enum PoolSlot {
     SLOT_SELECT_WORK = 58, SLOT_SELECT_NORMS = 59, SLOT_SELECT_INDEX = 60,
     // hits by target (transpose.hip): the transpose's figure, sort keys and sort storage; the tally's figure
     SLOT_TRANSPOSE_WORK = 61, SLOT_TALLY_WORK = 62,
-    POOL_SLOTS = 63
+    // merged hits (merge.hip): the check's figures, the table of the parts, the summed offsets and the parts' places; the sort path's keys,
+    // placed payloads, heads, scan and sort storage; the copies of parts that live on another device
+    SLOT_MERGE_WORK = 63, SLOT_MERGE_SORT = 64, SLOT_MERGE_PEER = 65,
+    POOL_SLOTS = 66
 };
 
 struct bsk_ctx {

@@ -459,6 +459,22 @@ class SearchHits : public Owned<bsk_hits, bsk_hits_release> {
     int tally(Engine &e, uint64_t n_targets, bool add, Tally &into) const {
         return bsk_hits_tally(e.ctx(), p_, n_targets, add ? (uint32_t)BSK_TALLY_ADD : 0u, &into.handle());
     }
+    // one SearchHits out of the hits of several searches of the same queries (bsk_hits_merge): row q holds every hit of row q of every
+    // part with base[p] added to its target (base empty: all 0), strictly ascending, with every payload all parts carry; a pair that
+    // occurs twice is BSK_ERR_ARG unless add, which sums its fields, saturating.  Parts may belong to other engines.  into: empty, or
+    // any hits of this engine that are not among the parts
+    static int merge(Engine &e, const std::vector<const SearchHits *> &parts, const std::vector<uint64_t> &base, bool add, SearchHits &into) {
+        if (parts.empty() || (!base.empty() && base.size() != parts.size())) return BSK_ERR_ARG;
+        std::vector<const bsk_hits *> hs;
+        for (const SearchHits *p : parts) hs.push_back(p ? p->get() : nullptr);
+        return bsk_hits_merge(e.ctx(), hs.data(), base.empty() ? nullptr : base.data(), (uint32_t)hs.size(), add ? (uint32_t)BSK_MERGE_ADD : 0u, &into.handle());
+    }
+    // ... as a new object: empty (get() == nullptr) when the call failed, and the engine's error says why
+    static SearchHits merge(Engine &e, const std::vector<const SearchHits *> &parts, const std::vector<uint64_t> &base, bool add) {
+        SearchHits out;
+        (void)merge(e, parts, base, add, out);
+        return out;
+    }
     const uint32_t *members_device() const {  // nullptr for hits without members
         const uint32_t *m = nullptr;
         bsk_hits_members_device(p_, &m);

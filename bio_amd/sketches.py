@@ -1518,6 +1518,60 @@ class Engine(_Owner):
         res._bind(h, np.zeros(len(offsets) - 1, np.uint64), np.zeros(0, np.uint64))
         return res
 
+    def merge_hits(self, parts: Sequence["Hits"], target_base=None, add: bool = False, reuse: Optional["Hits"] = None) -> "Hits":
+        """One Hits out of the hits of several searches of the same queries (bsk_hits_merge): a database split over many indexes.
+        Row q holds every hit of row q of every part with target_base[p] added to its target, strictly ascending, with every payload
+        all parts carry.  target_base: default the running sum of len(part.target_sizes) -- shards by target, shard p holds the
+        targets behind those of the shards before it.  Shards by value (every shard holds all targets and part of the hash space):
+        target_base=[0] * len(parts) and add=True, which sums the fields of a pair that several parts report, saturating; without
+        add such a pair is an error.  Search the value shards with min_shared=1 and filter("shared", m) the merged hits: the
+        threshold is on the sum.  The parts may belong to other engines, on this device or another; at most 64 parts.
+        The result's query_sizes are those of parts[0] (unequal ones raise ValueError); target_sizes[base_p + i] +=
+        part_p.target_sizes[i].  The weighted side is a snapshot taken now: with weights on every part, every part's norms are
+        resolved (a part that cannot raises the ValueError of its own formulas), the query norms are those of parts[0] and the target
+        norms are added at base_p like the sizes, saturating.  reuse: any Hits of this engine that is not among the parts."""
+        parts = list(parts)
+        P = len(parts)
+        if target_base is None:
+            base = np.zeros(P, np.uint64)
+            base[1:] = np.cumsum([len(p.target_sizes) for p in parts[:-1]], dtype=np.uint64)
+        else:
+            base = np.array([int(b) for b in target_base], np.uint64)  # (a negative or a 65-bit base raises here)
+            if base.shape != (P,):
+                raise ValueError("merge_hits: target_base needs one entry per part")
+        snap = None
+        if P:
+            if any(not np.array_equal(p.query_sizes, parts[0].query_sizes) for p in parts[1:]):
+                raise ValueError("merge_hits: the parts differ in their query_sizes: they are not hits of the same queries")
+            for what in ("_plain_targets", "_flip"):
+                if any(getattr(p, what) != getattr(parts[0], what) for p in parts[1:]):
+                    raise ValueError("merge_hits: the parts differ in " + what.strip("_") + " (hits against counted and plain indexes, or transposed and not)")
+            n = max(int(b) + len(p.target_sizes) for b, p in zip(base, parts))
+            top = np.uint64(np.iinfo(np.uint64).max)
+
+            def spread(arrays):  # arrays[p] added at base[p], saturating
+                out = np.zeros(n, np.uint64)
+                for b, a in zip(base, arrays):
+                    a = np.asarray(a, np.uint64)
+                    s = out[int(b):int(b) + len(a)]
+                    t = s + a
+                    t[t < a] = top
+                    s[:] = t
+                return out
+
+            sizes = spread([p.target_sizes for p in parts])
+            norms = None
+            if all(p.has_weights() for p in parts):
+                each = [p._norm_arrays("merge_hits") for p in parts]
+                norms = (each[0][0], spread([x[1] for x in each]), each[0][2], spread([x[3] for x in each]))
+            snap = (parts[0].query_sizes, sizes, norms, parts[0]._plain_targets, parts[0]._flip)
+        hs = (C.c_void_p * max(P, 1))(*[p.h for p in parts])
+        h = _take_over(self, reuse, lambda out: self.lib.bsk_hits_merge(self.ctx, hs, base.ctypes.data if P else None, P, L.MERGE_ADD if add else 0, out))
+        res = reuse if reuse is not None else Hits(self)
+        res._bind(h, snap[0], snap[1])
+        res._norms, res._plain_targets, res._flip = snap[2:]
+        return res
+
     def sets_from_arrays_counted(self, offsets: np.ndarray, values: np.ndarray, counts: np.ndarray) -> Sets:
         """sets_from_arrays with counts[len(values)] (u32, none of them 0): bsk_sets_from_host_counted"""
         offsets = np.ascontiguousarray(offsets, np.uint64)

@@ -503,6 +503,9 @@ int bsk_result_sets(bsk_ctx *ctx, const bsk_result *r, int scope, int scale, bsk
  *   bsk_hits_transpose, bsk_hits_tally (bsk_tally **out): every BSK_ERR_ARG -- a target >= n_targets included, which one small device
  *     pass finds before the object is taken over, and for the tally a flag bit and a table of another n_targets -- and the 2^32 limits
  *     keep the slot; BSK_ERR_NOMEM and BSK_ERR_DEVICE release.
+ *   bsk_hits_merge: every BSK_ERR_ARG -- a duplicate without BSK_MERGE_ADD included, which the device passes find before the object is
+ *     taken over -- and every BSK_ERR_UNSUPPORTED -- the 2^32 limits and a target_base + target beyond 32 bits -- keep the slot;
+ *     BSK_ERR_NOMEM and BSK_ERR_DEVICE release.
  *   bsk_result_sets_windows: as bsk_sets_compare -- every BSK_ERR_ARG keeps the slot; both 2^32 limits (BSK_ERR_UNSUPPORTED: the windows in
  *     total, the gathered tuples), known after a read-back, release it, as BSK_ERR_NOMEM and BSK_ERR_DEVICE do.
  *   bsk_result_sets_reuse, _counted: a NULL `sets` and sets of another context (BSK_ERR_ARG) keep the slot.  Every other error releases:
@@ -961,6 +964,50 @@ int bsk_tally_fetch(bsk_ctx *ctx, const bsk_tally *t, uint64_t first, uint64_t c
                     uint64_t *rows, uint64_t *unique, uint64_t *shared);   /* any may be NULL */
 int bsk_tally_device(const bsk_tally *t, const uint64_t **rows, const uint64_t **unique, const uint64_t **shared);
 void bsk_tally_release(bsk_tally *t);
+
+/* ---- merged hits: one bsk_hits out of the hits of several searches ----
+ * An index holds fewer than 2^32 postings and lives on one device; a database beyond that is split into shards, every shard is
+ * searched, and bsk_hits_merge joins the results where they are (kmcp merge; sourmash over several databases) -- with every payload,
+ * which the route over the host and bsk_hits_from_host drops.  Two ways to shard, one entry: by target (shard p holds the targets
+ * target_base[p] .. target_base[p] + T_p - 1: a row of the result is the union of the parts' rows) and by value (every shard holds all
+ * targets and a range of the hash space: equal bases, and the integers of a pair that several shards report add up, BSK_MERGE_ADD).
+ * It chooses no policy and composes with everything that takes hits.
+ *
+ * All parts have the same n_queries and the result has those rows.  Row q of the result holds every hit of row q of every part with
+ * target' = target + target_base[p] (target_base == NULL: all 0), strictly ascending by target'.  The rows of the parts need not be
+ * ascending: the output of bsk_hits_top / _top_by is legal input, so a caller may cut every shard's hits to its n best, merge, and
+ * take the n best again.  Two hits of one result row with the same target' -- across parts or inside one part, which nothing the
+ * library produces has -- are BSK_ERR_ARG without BSK_MERGE_ADD; with it they become one hit whose fields are the sums, each
+ * saturating at its type's maximum: shared, total and members at 2^32 - 1, dot and min_sum at 2^64 - 1.  Saturating sums of
+ * non-negative integers do not depend on their order: the result is a function of the inputs alone.  The result carries a payload
+ * (total; dot and min_sum; members) if and only if every part carries it; a re-used *out of any history ends with exactly those flags.
+ * One part with a base is a relabelling.
+ * Parts of ctx are read in place; a part of another context on the same device is read in place after the entry has synchronised
+ * that context's stream on the host; a part on another device is copied once into ctx's pool with the peer copy bsk_index_attach
+ * uses.  The caller must not write or release a part during the call.  *out is NULL or an object of ctx and not one of the parts.
+ * BSK_ERR_ARG, all of which keep the slot, in this order: a NULL ctx, parts or out; n_parts == 0 or > BSK_MERGE_MAX_PARTS; any flag
+ * bit but BSK_MERGE_ADD; a NULL parts[p]; rows that differ between parts; *out among the parts; *out of another context; a
+ * target_base[p] >= 2^32; and, found on the device before the object is taken over, a duplicate without BSK_MERGE_ADD.
+ * BSK_ERR_UNSUPPORTED, which keeps the slot too: 2^32 rows or more, 2^32 hits in total or more, and some target_base[p] + target
+ * >= 2^32 (known from the check pass, before the object is taken over).  BSK_ERR_NOMEM and BSK_ERR_DEVICE release it.  n_queries == 0
+ * and parts that are all empty give empty results with BSK_OK.
+ * How it runs: a small pass per part (k_mg_check, a lane per hit, one ballot per trip of a wavefront) finds the part's smallest and
+ * largest target and whether every row is strictly ascending; the host reads one block of figures.  The output offsets before any
+ * combining are the sum of the parts' offsets: no scan.  path=concat, when every part has ascending rows and the shifted target
+ * ranges of the non-empty parts are disjoint and increase with p (the shards by target): k_mg_starts writes per part and row where
+ * the part's hits begin, a lane per row over at most 64 parts whose pointers live in a pool array; k_mg_place, a lane per input hit,
+ * finds the hit's row by a search of its part's offsets and writes target + base, shared and every carried payload once.  Every
+ * array is read once and written once: no sort, no atomics, no row walked by one lane; duplicates cannot exist here.  path=sort, for
+ * everything else: the same placement into pool scratch with the key (target' << idx_bits) | place, every key distinct, so
+ * nothing rests on the sort being stable; the library's segmented key sort over the rows; a head where a row starts or target'
+ * changes (k_mg_heads); the library's scan over the heads; every head's owner gathers its run by the keys' low bits, sums it and
+ * places it (k_mg_runs).  The result is bit-identical from call to call on both paths.  bsk_hits_plan names the kernels and reports
+ * path=concat|sort, parts=, hits= (those of the parts in total) and combined= (hits - the result's hits) as decimal figures;
+ * n_large_queries is 0. */
+enum { BSK_MERGE_ADD = 1 };
+enum { BSK_MERGE_MAX_PARTS = 64 };
+int bsk_hits_merge(bsk_ctx *ctx, const bsk_hits *const *parts, const uint64_t *target_base /* host, [n_parts], or NULL: all 0 */,
+                   uint32_t n_parts, uint32_t flags, bsk_hits **out);
 
 /* ---- clusters of a neighbour graph: connected components and greedy representatives ----
  * (bsk_sets_neighbors, which makes such a graph from sets, is declared below this block: it closes the header.)
